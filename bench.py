@@ -17,8 +17,14 @@ on rank i mod N) and the per-frame digests + verdicts go to rank 0 over RCCL in 
 batch of point-to-point transfers per round), overlapped with the later rounds' kernels; no other
 collective. Rank 0 receives the shards as they are (global frame j*N + r is local frame j
 of rank r: seqs_amd.shard.gather_digests shows the interleave; the bench does not spend a
-rank-0 kernel on it). With N > 1 the same line also carries "c4_strong": the C4 strong-scaled
+rank-0 kernel on it). With --full and N > 1 the same line also carries "c4_strong": the C4 strong-scaled
 measurement (BASELINE configs[3], the config the >= 3.5x-at-4-GPUs target is quoted on).
+
+A plain run sets up, warms up, times --steps steps and prints the line. --full adds what takes runs
+of its own: the CPU baselines, the kernel-only pass between HIP events (roofline achieved / frac /
+kernel_avg_us), the sub-records beside the C2 headline and the C4 record. --dump-outputs DIR writes
+what the last timed step returned as DIR/<name>.npy (the batches are seeded: the same arguments
+give the same inputs, so two builds can be compared output for output).
 
 Prints ONE JSON line on rank 0 (see the contract in DESIGN.md §5).
 """
@@ -181,7 +187,41 @@ def parse():
                    help="HIP streams the steps rotate over: step i+1's kernel starts on the CUs step i's "
                         "tail frees (every batch is still fully digested). 5 measured best on the 4 hardware "
                         "queues of the box (DESIGN.md §5.1)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the CPU baselines, the kernel-only pass between HIP events (the "
+                        "roofline's achieved / frac / kernel_avg_us and the PMC traffic), the C3 / C5 / small / fill / "
+                        "fcs sub-records (N = 1) and the C4 strong-scaled record (N > 1). Without it a run sets up, "
+                        "warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned (rank 0: its digest words "
+                        "and verdicts; --op fill: a sample of the filled frames too) as DIR/<name>.npy")
     return p.parse_args()
+
+
+DUMP_LIMIT = 60_000_000  # array bytes --dump-outputs writes at most, over all its files (under 64 MB with headers)
+
+
+def dump_outputs(path: str, arrays: dict):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 for 8- and 16-bit integers and
+    float64 for wider ones (both exact); a structured array one file per field. The arrays share
+    DUMP_LIMIT equally: of a larger one a fixed sample is written (elements at sorted flat indices
+    drawn with seed 0, the same from run to run)."""
+    flat = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.fields:
+            for f in a.dtype.fields:
+                flat[f"{name}_{f}"] = a[f]
+        else:
+            flat[name] = a
+    os.makedirs(path, exist_ok=True)
+    room = DUMP_LIMIT // max(1, len(flat))
+    for name, a in flat.items():
+        a = np.ascontiguousarray(a).astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        keep = room // a.dtype.itemsize
+        if a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def make_batch(cfg: str, n: int, seed: int):
@@ -537,29 +577,63 @@ def main():
                 got = recv[b][q][: m * slab].view(m, slab)[:, 8 * n : 9 * n]
                 assert int(got.max().item()) == 0, f"rank {q}'s round-{b} slabs did not arrive"
 
-    # ---- kernel-only timing with HIP events on the launch stream (roofline.achieved): one event
-    # pair around K back-to-back launches on one stream (no overlap with another launch), so the
-    # average is the kernel's duration plus the stream's dispatch gap; an event pair around every
-    # launch would add each record's own latency to every launch.
-    k0, k1 = GPU.event(), GPU.event()
-    with GPU.use(main_stream):
-        k0.record(main_stream)
-        for i in range(args.steps):  # same stream, in order: no slot events needed
-            launch(i % nb, outs[i % nslot], stats[i % nslot], main_stream)
-        k1.record(main_stream)
-    GPU.sync()
-    k_avg_ms = k0.elapsed_time(k1) / args.steps
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # what the region's last step returned (before any later launch writes its slot again)
+        if gather:
+            k, j = plans[args.steps][1][args.steps - 1]
+            o, st = rviews[k % 2][j]
+        else:
+            o, st = outs[(args.warmup + args.steps - 1) % nslot], stats[(args.warmup + args.steps - 1) % nslot]
+        dumped = {"digest_words": o.cpu().numpy(), "verdicts": st.cpu().numpy()}
+        if args.op == "fill":  # the fill's result is the frames themselves, rewritten in place
+            dumped["frames"] = batches[(args.warmup + args.steps - 1) % nb][0].cpu().numpy()
+        dump_outputs(args.dump_outputs, dumped)
+        del dumped
+
     engine_last_kernel = engine.last_kernel()
+    k_avg_ms = None
+    if args.full:
+        # ---- kernel-only timing with HIP events on the launch stream (roofline.achieved): one event
+        # pair around K back-to-back launches on one stream (no overlap with another launch), so the
+        # average is the kernel's duration plus the stream's dispatch gap; an event pair around every
+        # launch would add each record's own latency to every launch.
+        k0, k1 = GPU.event(), GPU.event()
+        with GPU.use(main_stream):
+            k0.record(main_stream)
+            for i in range(args.steps):  # same stream, in order: no slot events needed
+                launch(i % nb, outs[i % nslot], stats[i % nslot], main_stream)
+            k1.record(main_stream)
+        GPU.sync()
+        k_avg_ms = k0.elapsed_time(k1) / args.steps
+        engine_last_kernel = engine.last_kernel()
 
     total_bytes = bytes_per_batch * args.steps * world
     value = total_bytes / elapsed / GIB
-    achieved_gbs = bytes_per_batch / (k_avg_ms * 1e-3) / 1e9
-    traffic, traffic_cal = load_pmc_traffic(args.config) if args.op == "digest" else (None, None)
+    kernel_only = {}  # the roofline figures of the kernel-only pass and the PMC traffic beside them (--full)
+    if args.full:
+        achieved_gbs = bytes_per_batch / (k_avg_ms * 1e-3) / 1e9
+        traffic, traffic_cal = load_pmc_traffic(args.config) if args.op == "digest" else (None, None)
+        kernel_only = {
+            "achieved": round(achieved_gbs, 1),
+            "frac": round(achieved_gbs / HBM_PEAK_GBS, 4),
+            "frac_mode": "single stream: algorithmic bytes / average kernel duration (HIP events around K "
+                         "back-to-back launches on one stream, no overlap between launches)",
+            "traffic": traffic,
+            "traffic_calibrated": traffic_cal,
+            "traffic_note": "traffic = (2*FETCH_SIZE + WRITE_SIZE)*1024 per launch (profiles/pmc_<cfg>.json, separate "
+                            "--pmc passes). Its excess over the algorithmic bytes is mostly the read pattern's own: "
+                            "the line two neighbouring frames share is fetched twice (~8.4% on C2); "
+                            "traffic_calibrated divides that pattern factor out (the kernel's excess beyond it)"
+            if traffic is not None else None,
+            "kernel_avg_us": round(k_avg_ms * 1e3, 3),
+            "kernel_timing": "HIP events around K back-to-back launches on the launch stream",
+            "achieved_incl_metadata": round((bytes_per_batch + 21 * n) / (k_avg_ms * 1e-3) / 1e9, 1),
+        }
 
     result = None
     if rank == 0:
         cpu = None
-        if world == 1 and args.cpu_seconds > 0 and args.op == "digest":
+        if args.full and world == 1 and args.cpu_seconds > 0 and args.op == "digest":
             cpu = cpu_baseline(args.config, args.cpu_seconds, args.cpu_threads)
         result = {
             "metric": "GiB/s device-resident CRC-32+Internet-csum over batched MTU frames; % HBM peak",
@@ -590,22 +664,12 @@ def main():
             },
             "roofline": {
                 "bound": "hbm",
-                "achieved": round(achieved_gbs, 1),
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
-                "frac": round(achieved_gbs / HBM_PEAK_GBS, 4),
-                "frac_mode": "single stream: algorithmic bytes / average kernel duration (HIP events around K "
-                             "back-to-back launches on one stream, no overlap between launches)",
                 "frac_whole_job": round(bytes_per_batch / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
                 "frac_whole_job_mode": f"algorithmic bytes per step / ms_per_step of the timed region ({ns} streams: "
                                        "consecutive launches overlap each other's start and tail)",
-                "traffic": traffic,
-                "traffic_calibrated": traffic_cal,
-                "traffic_note": "traffic = (2*FETCH_SIZE + WRITE_SIZE)*1024 per launch (profiles/pmc_<cfg>.json, separate "
-                                "--pmc passes). Its excess over the algorithmic bytes is mostly the read pattern's own: "
-                                "the line two neighbouring frames share is fetched twice (~8.4% on C2); "
-                                "traffic_calibrated divides that pattern factor out (the kernel's excess beyond it)"
-                if traffic is not None else None,
+                **kernel_only,
                 "kernel": {0: "automatic: digest_kernel_a (one-pass) for uniform batches, digest_kernel_ab for mixed "
                               "(digest_kernel_g when a mixed tile holds a frame beyond its pieces), "
                               "digest_kernel_s once the launches it has seen ran had no frame over 128 B",
@@ -614,13 +678,10 @@ def main():
                            8: "digest_kernel_s preferred (fs_ctx_set_kernel 8: until a launch meets a frame over 128 B, "
                               "then the automatic choice until short traffic resumes)"}.get(args.kernel),
                 "kernel_chosen": KERNEL_NAMES.get(engine_last_kernel),
-                "kernel_avg_us": round(k_avg_ms * 1e3, 3),
-                "kernel_timing": "HIP events around K back-to-back launches on the launch stream",
                 "algorithmic_bytes_per_launch": bytes_per_batch,
                 # per frame the kernel also reads its 12-B descriptor (offset, length) and writes its
                 # 9-B result (digest, verdict): not algorithmic bytes, but 45% of them at 47-B frames
                 "metadata_bytes_per_launch": 21 * n,
-                "achieved_incl_metadata": round((bytes_per_batch + 21 * n) / (k_avg_ms * 1e-3) / 1e9, 1),
             },
             "cpu_baseline": cpu,
         }
@@ -628,7 +689,7 @@ def main():
     del batches, flat
     if gather:
         del rbuf, rviews, recv
-    if rank == 0 and world == 1 and args.config == "c2" and args.op == "digest" and not args.no_sub:
+    if args.full and rank == 0 and world == 1 and args.config == "c2" and args.op == "digest" and not args.no_sub:
         # BASELINE configs[2] and [4] beside the C2 headline: the C3
         # mixed batch device-resident (same steps and warmup) and the C5 jumbo batch end to end
         # from pinned host memory; the reference's 47-B benchmark frames device-resident and
@@ -646,7 +707,7 @@ def main():
         result["fcs"] = sub_record_op(args, dev, "fcs")
         GPU.empty_cache()
         result["small_host"] = sub_record_small_host(args)
-    if world > 1 and args.config == "c2" and args.op == "digest" and not args.no_c4:
+    if args.full and world > 1 and args.config == "c2" and args.op == "digest" and not args.no_c4:
         # the C4 strong-scaled record beside the weak-scaled C2 value (same steps / warmup)
         GPU.empty_cache()
         c4 = run_c4(args, world, rank, local, dev, frames=args.c4_frames)
@@ -990,7 +1051,7 @@ def time_region(world, dist, torch, body, dev, streams=()):
 
 
 def main_c4(args, world, rank, local, dev):
-    result = run_c4(args, world, rank, local, dev, frames=args.frames or (1 << 20))
+    result = run_c4(args, world, rank, local, dev, frames=args.frames or (1 << 20), dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if dist_initialized():
@@ -1006,7 +1067,7 @@ def dist_initialized() -> bool:
     return dist.is_available() and dist.is_initialized()
 
 
-def run_c4(args, world, rank, local, dev, frames):
+def run_c4(args, world, rank, local, dev, frames, dump=None):
     """C4 (BASELINE configs[3]): one global batch of 1,048,576 x 1500-B frames per step,
     frame i on rank i mod N (strong scaling). A step: every rank digests its shard into a
     slab (digests + verdicts, fs_shard_slab_bytes layout), RCCL brings the slabs to rank 0 (one batch
@@ -1109,23 +1170,33 @@ def run_c4(args, world, rank, local, dev, frames):
         assert np.array_equal(gout[k].cpu().numpy(), exp_w), "de-interleave mismatch"
         assert np.array_equal(gst[k].cpu().numpy(), g[r * sb + 8 * m + j]), "de-interleave verdict mismatch"
         assert (gst[k].cpu().numpy() == 0).all(), "valid frames must all verify"
+        if dump:  # the last step's digests and verdicts in global frame order
+            dump_outputs(dump, {"digest_words": gout[k].cpu().numpy(), "verdicts": gst[k].cpu().numpy()})
 
-    # kernel-only: K back-to-back shard digests on one stream (events on the launch stream)
-    k0, k1 = GPU.event(), GPU.event()
-    ms = streams[0]
-    with GPU.use(ms):
-        k0.record(ms)
-        for i in range(args.steps):
-            fb, fo, fl = batches[i % nb]
-            o, st = views(0)
-            engine.digest_device(fb, fo, fl, mtu=0, out=o, status=st, stream=ms)
-        k1.record(ms)
-    GPU.sync()
-    k_ms = k0.elapsed_time(k1) / args.steps
-    t = torch.tensor([k_ms], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    k_ms_max = float(t.item())
+    kernel_only, kernel_only_config = {}, {}
+    if args.full:
+        # kernel-only: K back-to-back shard digests on one stream (events on the launch stream)
+        k0, k1 = GPU.event(), GPU.event()
+        ms = streams[0]
+        with GPU.use(ms):
+            k0.record(ms)
+            for i in range(args.steps):
+                fb, fo, fl = batches[i % nb]
+                o, st = views(0)
+                engine.digest_device(fb, fo, fl, mtu=0, out=o, status=st, stream=ms)
+            k1.record(ms)
+        GPU.sync()
+        k_ms = k0.elapsed_time(k1) / args.steps
+        t = torch.tensor([k_ms], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        k_ms_max = float(t.item())
+        kernel_only = {"achieved": round(bytes_local / (k_ms * 1e-3) / 1e9, 1),
+                       "frac": round(bytes_local / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                       "kernel_avg_us": round(k_ms * 1e3, 3),
+                       "frac_mode": "rank 0's shard kernel, single stream"}
+        kernel_only_config = {"kernel_only_gibs": round(bytes_global / (k_ms_max * 1e-3) / GIB, 3),
+                              "kernel_only_ms": round(k_ms_max, 5)}
     value = bytes_global * args.steps / elapsed / GIB
     if rank == 0:
         result = {
@@ -1149,23 +1220,19 @@ def run_c4(args, world, rank, local, dev, frames):
                 "parallelism": f"frame i on rank i mod {world}; per step: shard digest, RCCL gather of the digests + "
                                "verdicts to rank 0, de-interleave kernel on rank 0 (all inside the step)"
                 if world > 1 else "single GPU: shard = whole batch; de-interleave kernel inside the step",
-                "kernel_only_gibs": round(bytes_global / (k_ms_max * 1e-3) / GIB, 3),
-                "kernel_only_ms": round(k_ms_max, 5),
+                **kernel_only_config,
                 "streams": 2,
             },
             "roofline": {
                 "bound": "hbm",
-                "achieved": round(bytes_local / (k_ms * 1e-3) / 1e9, 1),
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
-                "frac": round(bytes_local / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                 "traffic": None,
                 "kernel": "automatic choice (uniform 1500-B shards: digest_kernel_a, the one-pass kernel)",
-                "kernel_avg_us": round(k_ms * 1e3, 3),
-                "frac_mode": "rank 0's shard kernel, single stream",
+                **kernel_only,
             },
             "cpu_baseline": cpu_baseline("c4", args.cpu_seconds, args.cpu_threads)
-            if world == 1 and args.cpu_seconds > 0 else None,
+            if args.full and world == 1 and args.cpu_seconds > 0 else None,
         }
     else:
         result = None
@@ -1224,8 +1291,11 @@ def main_c5(args):
                      "achieved": round(total / (elapsed / args.steps) / 1e9, 2),
                      "frac": round(total / (elapsed / args.steps) / 1e9 / (63.0 * ngpu), 4),
                      "kernel": None, "note": "PCIe Gen5 x16 spec 63 GB/s per GPU (MI355X_MICROARCH.md)"},
-        "cpu_baseline": cpu_baseline("c5", args.cpu_seconds, args.cpu_threads) if args.cpu_seconds > 0 else None,
+        "cpu_baseline": cpu_baseline("c5", args.cpu_seconds, args.cpu_threads)
+        if args.full and args.cpu_seconds > 0 else None,
     }
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, {"digests": out, "verdicts": st})
     print(json.dumps(result), flush=True)
     for e in engines:
         e.close()

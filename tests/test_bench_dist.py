@@ -37,12 +37,49 @@ def _run(args, world=2):
 
 def test_c2_weak_line_with_c4_record():
     d = _run(["--gpus", "2", "--steps", "20", "--warmup", "5", "--frames", "512", "--c4-frames", "4096",
-              "--cpu-seconds", "0", "--min-warm", "0"])
+              "--cpu-seconds", "0", "--min-warm", "0", "--full"])
     assert d["n_gpus"] == 2 and d["steps"] == 20 and d["scaling"] == "weak"
     assert d["config"]["global_batch_frames"] == 1024 and "RCCL" in d["config"]["parallelism"]
     c4 = d["c4_strong"]
     assert c4["scaling"] == "strong" and c4["config"]["global_batch_frames"] == 4096
     assert c4["value"] > 0 and c4["ms_per_step"] > 0
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line holds the headline alone (no C4 record, no kernel-only pass, no CPU
+    baseline); --dump-outputs writes rank 0's last timed step, the same from run to run."""
+    import numpy as np
+
+    args = ["--gpus", "2", "--steps", "11", "--warmup", "5", "--frames", "512", "--min-warm", "0"]
+    dumps = []
+    for k in range(2):
+        d = _run(args + ["--dump-outputs", str(tmp_path / f"run{k}")])
+        assert d["steps"] == 11 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "GiB/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "u8" and "GiB/s" in d["metric"]
+        assert "c4_strong" not in d and d["cpu_baseline"] is None and "kernel_avg_us" not in d["roofline"]
+        dumps.append({f: np.load(tmp_path / f"run{k}" / f) for f in sorted(os.listdir(tmp_path / f"run{k}"))})
+    assert sorted(dumps[0]) == ["digest_words.npy", "verdicts.npy"]
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, dumps[1][f])
+    # the stand-in engine's digest of rank 0: (frame length, rank + 1), verdict 0
+    assert np.array_equal(dumps[0]["digest_words.npy"], np.tile([1500.0, 1.0], (512, 1)))
+    assert dumps[0]["verdicts.npy"].shape == (512,) and not dumps[0]["verdicts.npy"].any()
+
+
+def test_dump_outputs_samples_past_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4000)
+    big = np.arange(3000, dtype=np.int32).reshape(1500, 2)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), {"big": big, "small": np.arange(7, dtype=np.uint8)})
+    a, b = np.load(tmp_path / "0" / "big.npy"), np.load(tmp_path / "1" / "big.npy")
+    assert a.dtype == np.float64 and a.shape == (250,) and np.array_equal(a, b) and (np.diff(a) > 0).all()
+    s = np.load(tmp_path / "0" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, np.arange(7))
+    assert sum(os.path.getsize(tmp_path / "0" / f) for f in os.listdir(tmp_path / "0")) <= 4000 + 2 * 128
 
 
 def test_c4_config_line():

@@ -58,7 +58,7 @@ def main() -> None:
                 e = dict(os.environ)
                 e.update(env)
                 cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", str(a.warmup),
-                       "--cpu-seconds", "0", "--no-sub"] + extra + a.extra.split()
+                       "--full", "--cpu-seconds", "0", "--no-sub"] + extra + a.extra.split()
                 cp = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=180)
                 if cp.returncode != 0:
                     print(f"{name}: rc {cp.returncode}\n{cp.stderr[-2000:]}", flush=True)

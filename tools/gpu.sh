@@ -52,8 +52,8 @@ for step in "$@"; do
     timeout -k 10 400 python bench.py $arg > $O/bench_$i.json 2> $O/bench_$i.err || { echo "FAIL bench $arg"; tail -5 $O/bench_$i.err; exit 1; }
     echo "bench $arg: $(summ $O/bench_$i.json)" ;;
   prof)
-    rm -rf gpurun_out/prof
-    timeout -k 10 900 bash tools/gpu_prof.sh > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 1; }
+    rm -rf $O/prof
+    OUT=$O timeout -k 10 900 bash tools/gpu_prof.sh > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 1; }
     tail -4 $O/prof.log ;;
   driver_prof)
     (cd /tmp && timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/driver_cmd -o run -- python3 $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $GRAFT_REPO_ROOT/$O/driver_prof.json 2> $GRAFT_REPO_ROOT/$O/driver_prof.err) || { echo FAIL driver_prof; tail -5 $O/driver_prof.err; exit 1; }

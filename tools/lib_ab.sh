@@ -9,10 +9,10 @@ for rep in $(seq 1 ${REPS:-2}); do
   for v in "$@"; do
     L=$PWD/seqs_amd/lib/ab/libframesum_$v.so; [ "$v" = prod ] && L=$PWD/seqs_amd/lib/libframesum.so
     for c in ${CFGS:-drv c2 c3}; do case $c in
-      drv) FRAMESUM_LIB=$L run ${v}_drv python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 ;;
-      c2) FRAMESUM_LIB=$L run ${v}_c2 python bench.py --steps 2000 --warmup 500 --cpu-seconds 0 ;;
-      c3) FRAMESUM_LIB=$L run ${v}_c3 python bench.py --config c3 --steps 1000 --warmup 500 --cpu-seconds 0 ;;
-      fill) FRAMESUM_LIB=$L run ${v}_fill python bench.py --op fill --steps 1000 --warmup 500 --cpu-seconds 0 ;;
+      drv) FRAMESUM_LIB=$L run ${v}_drv python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --full ;;
+      c2) FRAMESUM_LIB=$L run ${v}_c2 python bench.py --steps 2000 --warmup 500 --cpu-seconds 0 --full ;;
+      c3) FRAMESUM_LIB=$L run ${v}_c3 python bench.py --config c3 --steps 1000 --warmup 500 --cpu-seconds 0 --full ;;
+      fill) FRAMESUM_LIB=$L run ${v}_fill python bench.py --op fill --steps 1000 --warmup 500 --cpu-seconds 0 --full ;;
     esac; done
   done
 done
