@@ -243,7 +243,7 @@ fs_status fs_deinterleave(fs_ctx* ctx, const uint8_t* gathered, uint32_t nshards
  *   8: the small-frame kernel preferred: it runs until a launch reports a frame over 128 bytes,
  *     then the automatic choice among the others until 2 launches have run short again.
  * The host-staged calls see every length: with 0 or 8 a batch whose frames are all <= 128 bytes
- * runs the small-frame kernel; with 0 a batch whose lengths all lie within 256 bytes of each other
+ * runs the small-frame kernel; with 0 or 8 a batch whose lengths all lie within 256 bytes of each other
  * runs the one-pass kernel from the context's first call; any other batch the automatic choice. A
  * TX fill never runs the small-frame kernel. Because reports arrive late, a launch of the
  * small-frame kernel can still meet long frames: they stay correct there but one lane streams each

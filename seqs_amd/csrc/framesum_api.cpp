@@ -55,12 +55,13 @@ struct fs_ctx {
     // the path the latest fs_digest_batch_host took (fs_test_last_host_path): 1 staged in one
     // chunk, 2 read in place, 3 chunked
     int last_host_path = 0;
-    // host-mapped word the kernels set when a batch has widely mixed lengths (launch_digest)
+    // the host-mapped block the kernels post their reports to (framesum_choice.h), and what the
+    // context remembers of them between launches
     volatile uint32_t* h_report = nullptr;
     uint32_t* d_report = nullptr;
+    framesum::ChoiceState choice;
     int force_kernel = 0;  // fs_ctx_set_kernel
     int workgroups = 0;    // fs_ctx_set_workgroups (0: one per CU)
-    uint32_t next_launch_id = 1;  // the context's launch sequence (launch_digest: report ids, sticky window)
     HostSlot slot[kHostSlots];
     hipStream_t copy_stream = nullptr, compute_stream = nullptr;
     hipStream_t copy_stream2 = nullptr;  // the odd chunks' frame copies
@@ -234,23 +235,57 @@ hipError_t launch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, c
                   uint8_t* wframes, uint32_t tx, int force = -1) {
     const int wgs = ctx->workgroups > 0 && ctx->workgroups < ctx->num_cus ? ctx->workgroups : ctx->num_cus;
     return framesum::launch_digest(frames, offsets, lengths, n, mtu, ctx->d_tables, out, status, stream, wgs,
-                                   ctx->h_report, ctx->d_report, &ctx->next_launch_id,
+                                   ctx->choice, ctx->h_report, ctx->d_report,
                                    force >= 0 ? force : ctx->force_kernel, op, wframes, tx);
 }
 
-// The host-staged digest sees the batch's lengths on the host: with the automatic choice (0) or the
-// short-frame preference (8), a batch whose frames are all this short runs the small-frame kernel
-// (one lane per frame; its header slot holds frames up to ~130 B), and any other batch the
-// automatic choice between the 4-lane kernels. (A device-resident batch's lengths are in device
-// memory: there launch_digest chooses from the kernels' reports.)
-constexpr uint32_t kSmallAutoMaxLen = framesum::kSmallMaxLen;
-int host_force(const fs_ctx* ctx, uint32_t max_len, uint32_t min_len) {
-    if (ctx->force_kernel != 0 && ctx->force_kernel != 8) return ctx->force_kernel;
-    if (max_len <= kSmallAutoMaxLen) return framesum::kForceSmallExact;
-    // a longer frame: the 4-lane choice, never the small-frame kernel, even after a
-    // streak of short device-resident launches; lengths within kUniformSpan: the one-pass kernel from
-    // the first call (a short-lived RecvEthBatch context)
-    return max_len - min_len < framesum::kUniformSpan ? framesum::kForceUniformHost : framesum::kForceNoSmall;
+// The argument checks at the head of a batch entry point `fn` (`aligned`: the kernel reads `frames`
+// itself, so they must be 4-byte aligned). An empty batch passes: the caller returns FS_SUCCESS.
+fs_status check_batch(fs_ctx* ctx, const char* fn, const void* frames, const void* offsets, const void* lengths,
+                      uint32_t n, const void* out, bool aligned) {
+    if (n == 0) return FS_SUCCESS;
+    if (n > kMaxFrames) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": n too large (at most 2^31 frames per call)");
+    if (!frames || !offsets || !lengths || !out) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");
+    if (aligned && (reinterpret_cast<uintptr_t>(frames) & 3u))
+        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": frames must be 4-byte aligned");
+    return FS_SUCCESS;
+}
+
+// The device address of pinned host memory [p, p + bytes) the kernel can read or write directly, or
+// null.
+void* mapped(void* p, size_t bytes) {
+    if (!p || !is_pinned(p, bytes)) return nullptr;
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return d;
+}
+
+// Where the one launch of a host-staged call writes its n digests and verdicts: straight to host
+// memory (mapped pinned memory: no D2H copy, no gap before it), into the caller's arrays when they
+// are pinned, else into the context's pinned mirror (ensure_pinned), which copy_out delivers after
+// the wait.
+struct ResultTarget {
+    fs_digest* d_out;
+    uint8_t* d_st;
+    bool direct;
+};
+ResultTarget result_target(const fs_ctx* ctx, fs_digest* out, uint8_t* status, uint32_t n) {
+    void* d_out = mapped(out, (size_t)n * sizeof(fs_digest));
+    void* d_st = status ? mapped(status, n) : nullptr;
+    const bool direct = d_out && (!status || d_st);
+    if (!direct) {
+        d_out = ctx->d_pin + (size_t)n * 12;
+        d_st = status ? ctx->d_pin + (size_t)n * 20 : nullptr;
+    }
+    return ResultTarget{static_cast<fs_digest*>(d_out), static_cast<uint8_t*>(d_st), direct};
+}
+void copy_out(const fs_ctx* ctx, const ResultTarget& t, fs_digest* out, uint8_t* status, uint32_t n) {
+    if (t.direct) return;
+    std::memcpy(out, ctx->h_pin + (size_t)n * 12, (size_t)n * sizeof(fs_digest));
+    if (status) std::memcpy(status, ctx->h_pin + (size_t)n * 20, n);
 }
 
 }  // namespace
@@ -296,14 +331,7 @@ fs_status fs_ctx_create(int device, fs_ctx** out) {
         e = hipHostMalloc(&hp, 64, hipHostMallocMapped);
         if (e == hipSuccess) {
             ctx->h_report = static_cast<volatile uint32_t*>(hp);
-            ctx->h_report[framesum::kReportLatest] = 0u;
-            ctx->h_report[framesum::kReportInitial] = framesum::kInitialMixedLaunches;
-            ctx->h_report[framesum::kReportChosen] = 0u;
-            ctx->h_report[framesum::kReportSeen] = 0u;
-            ctx->h_report[framesum::kReportSeenSeq] = 0u;
-            for (int w : {framesum::kReportLong, framesum::kReportRan, framesum::kReportLongSeen,
-                          framesum::kReportRanSeen, framesum::kReportShort, framesum::kReportLongEver})
-                ctx->h_report[w] = 0u;
+            for (int w = 0; w < 16; ++w) ctx->h_report[w] = 0u;
             e = hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->d_report), hp, 0);
         }
     }
@@ -363,11 +391,8 @@ fs_status fs_digest_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* of
                           uint32_t n, uint32_t mtu, fs_digest* out, uint8_t* status, void* stream) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    if (n == 0) return FS_SUCCESS;
-    if (n > kMaxFrames) return set_err(ctx, FS_E_INVALID, "fs_digest_batch: n too large (at most 2^31 frames per call)");
-    if (!frames || !offsets || !lengths || !out) return set_err(ctx, FS_E_INVALID, "fs_digest_batch: null pointer");
-    if (reinterpret_cast<uintptr_t>(frames) & 3u)
-        return set_err(ctx, FS_E_INVALID, "fs_digest_batch: frames must be 4-byte aligned");
+    const fs_status st = check_batch(ctx, "fs_digest_batch", frames, offsets, lengths, n, out, true);
+    if (n == 0 || st != FS_SUCCESS) return st;
     FS_HIP(ctx, hipSetDevice(ctx->device));
     FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, reinterpret_cast<hipStream_t>(stream), framesum::FsOp::kDigest, nullptr, 0));
     return FS_SUCCESS;
@@ -378,11 +403,8 @@ fs_status fs_fill_batch(fs_ctx* ctx, uint8_t* frames, const uint64_t* offsets, c
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
     if (flags & ~(uint32_t)(FS_FILL_CSUM | FS_FCS_APPEND)) return set_err(ctx, FS_E_INVALID, "fs_fill_batch: unknown flags");
-    if (n == 0) return FS_SUCCESS;
-    if (n > kMaxFrames) return set_err(ctx, FS_E_INVALID, "fs_fill_batch: n too large (at most 2^31 frames per call)");
-    if (!frames || !offsets || !lengths || !out) return set_err(ctx, FS_E_INVALID, "fs_fill_batch: null pointer");
-    if (reinterpret_cast<uintptr_t>(frames) & 3u)
-        return set_err(ctx, FS_E_INVALID, "fs_fill_batch: frames must be 4-byte aligned");
+    const fs_status st = check_batch(ctx, "fs_fill_batch", frames, offsets, lengths, n, out, true);
+    if (n == 0 || st != FS_SUCCESS) return st;
     FS_HIP(ctx, hipSetDevice(ctx->device));
     FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, reinterpret_cast<hipStream_t>(stream), framesum::FsOp::kFill, frames, flags));
     return FS_SUCCESS;
@@ -392,11 +414,8 @@ fs_status fs_digest_batch_fcs(fs_ctx* ctx, const uint8_t* frames, const uint64_t
                               uint32_t n, uint32_t mtu, fs_digest* out, uint8_t* status, void* stream) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    if (n == 0) return FS_SUCCESS;
-    if (n > kMaxFrames) return set_err(ctx, FS_E_INVALID, "fs_digest_batch_fcs: n too large (at most 2^31 frames per call)");
-    if (!frames || !offsets || !lengths || !out) return set_err(ctx, FS_E_INVALID, "fs_digest_batch_fcs: null pointer");
-    if (reinterpret_cast<uintptr_t>(frames) & 3u)
-        return set_err(ctx, FS_E_INVALID, "fs_digest_batch_fcs: frames must be 4-byte aligned");
+    const fs_status st = check_batch(ctx, "fs_digest_batch_fcs", frames, offsets, lengths, n, out, true);
+    if (n == 0 || st != FS_SUCCESS) return st;
     FS_HIP(ctx, hipSetDevice(ctx->device));
     FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, reinterpret_cast<hipStream_t>(stream), framesum::FsOp::kFcs, nullptr, 0));
     return FS_SUCCESS;
@@ -415,16 +434,15 @@ FS_HOST_CLONES static framesum::plan::ScanCore scan_descriptors(const uint64_t* 
     return framesum::plan::scan_core(offsets, lengths, n);
 }
 
-// The device address of pinned host memory [p, p + bytes) the kernel can read or write directly, or
-// null.
-static void* mapped(void* p, size_t bytes) {
-    if (!p || !is_pinned(p, bytes)) return nullptr;
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return d;
+// ... and the scan of a fs_digest_batch_host call, with the error set when a frame is out of range
+// (sc.bad < n).
+static framesum::plan::Scan scan_host(fs_ctx* ctx, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
+                                      uint64_t frames_bytes) {
+    const framesum::plan::Scan sc =
+        framesum::plan::scan_from(scan_descriptors(offsets, lengths, n), offsets, lengths, n, frames_bytes);
+    if (sc.bad < n)
+        set_err(ctx, FS_E_INVALID, "fs_digest_batch_host: frame " + std::to_string(sc.bad) + " ends past frames_bytes");
+    return sc;
 }
 
 // A host-staged batch that fits one staging chunk (path 1). Everything runs on the compute stream,
@@ -445,16 +463,7 @@ static fs_status host_single(fs_ctx* ctx, const uint8_t* frames, uint64_t frames
         drain_host_streams(ctx);
         return st;
     }
-    // The kernel writes the digests and verdicts straight to host memory (mapped pinned memory: no
-    // D2H copy, no gap before it): into the caller's arrays when they are pinned, else into the
-    // context's pinned mirror, copied out after the wait.
-    void* d_out = mapped(out, (size_t)n * sizeof(fs_digest));
-    void* d_st = status ? mapped(status, n) : nullptr;
-    const bool direct = d_out && (!status || d_st);
-    if (!direct) {
-        d_out = ctx->d_pin + (size_t)n * 12;
-        d_st = status ? ctx->d_pin + (size_t)n * 20 : nullptr;
-    }
+    const ResultTarget rt = result_target(ctx, out, status, n);
     const hipStream_t ks = ctx->compute_stream;
     // the frames behind the descriptors (issued by the caller before the scan), then the kernel, in
     // the compute stream's order: no cross-stream event between them
@@ -466,16 +475,13 @@ static fs_status host_single(fs_ctx* ctx, const uint8_t* frames, uint64_t frames
     const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(sl.d_frames) - cpy_lo);
     const uint64_t* d_off = reinterpret_cast<const uint64_t*>(ctx->d_desc);
     const uint32_t* d_len = reinterpret_cast<const uint32_t*>(ctx->d_desc + (size_t)n * 8);
-    FS_HIP_DRAIN(ctx, launch(ctx, base, d_off, d_len, n, mtu, reinterpret_cast<fs_digest*>(d_out),
-                       reinterpret_cast<uint8_t*>(d_st), ks, framesum::FsOp::kDigest, nullptr, 0, force));
+    FS_HIP_DRAIN(ctx, launch(ctx, base, d_off, d_len, n, mtu, rt.d_out, rt.d_st, ks, framesum::FsOp::kDigest, nullptr, 0,
+                             force));
     FS_HIP_DRAIN(ctx, hipEventRecord(sl.consumed, ks));
     sl.used = true;
     FS_HIP_DRAIN(ctx, hipEventRecord(ctx->host_done, ks));
     FS_HIP_DRAIN(ctx, host_wait(ctx->host_done));
-    if (!direct) {
-        std::memcpy(out, ctx->h_pin + (size_t)n * 12, (size_t)n * sizeof(fs_digest));
-        if (status) std::memcpy(status, ctx->h_pin + (size_t)n * 20, n);
-    }
+    copy_out(ctx, rt, out, status, n);
     ctx->host_dirty = false;
     return FS_SUCCESS;
 }
@@ -489,24 +495,14 @@ static fs_status host_inplace(fs_ctx* ctx, const uint8_t* d_frames, const uint64
     ctx->last_host_path = 2;
     fs_status st = ensure_pinned(ctx, n);
     if (st != FS_SUCCESS) return st;
-    void* d_out = mapped(out, (size_t)n * sizeof(fs_digest));
-    void* d_st = status ? mapped(status, n) : nullptr;
-    const bool direct = d_out && (!status || d_st);
-    if (!direct) {
-        d_out = ctx->d_pin + (size_t)n * 12;
-        d_st = status ? ctx->d_pin + (size_t)n * 20 : nullptr;
-    }
+    const ResultTarget rt = result_target(ctx, out, status, n);
     ctx->host_dirty = true;
     const hipStream_t ks = ctx->compute_stream;
-    FS_HIP_DRAIN(ctx, launch(ctx, d_frames, d_off, d_len, n, mtu, reinterpret_cast<fs_digest*>(d_out),
-                       reinterpret_cast<uint8_t*>(d_st), ks, framesum::FsOp::kDigest, nullptr, 0,
-                       framesum::kForceSmallExact));
+    FS_HIP_DRAIN(ctx, launch(ctx, d_frames, d_off, d_len, n, mtu, rt.d_out, rt.d_st, ks, framesum::FsOp::kDigest, nullptr,
+                             0, framesum::kForceSmallExact));
     FS_HIP_DRAIN(ctx, hipEventRecord(ctx->host_done, ks));
     FS_HIP_DRAIN(ctx, host_wait(ctx->host_done));
-    if (!direct) {
-        std::memcpy(out, ctx->h_pin + (size_t)n * 12, (size_t)n * sizeof(fs_digest));
-        if (status) std::memcpy(status, ctx->h_pin + (size_t)n * 20, n);
-    }
+    copy_out(ctx, rt, out, status, n);
     ctx->host_dirty = false;
     return FS_SUCCESS;
 }
@@ -515,10 +511,8 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
                                const uint32_t* lengths, uint32_t n, uint32_t mtu, fs_digest* out, uint8_t* status) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    if (n == 0) return FS_SUCCESS;
-    if (n > kMaxFrames) return set_err(ctx, FS_E_INVALID, "fs_digest_batch_host: n too large (at most 2^31 frames per call)");
-    if (!frames || !offsets || !lengths || !out)
-        return set_err(ctx, FS_E_INVALID, "fs_digest_batch_host: null pointer");
+    const fs_status ast = check_batch(ctx, "fs_digest_batch_host", frames, offsets, lengths, n, out, false);
+    if (n == 0 || ast != FS_SUCCESS) return ast;
     FS_HIP(ctx, hipSetDevice(ctx->device));
     fs_status pst = quiesce_host_streams(ctx);
     if (pst != FS_SUCCESS) return pst;
@@ -531,12 +525,10 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
         const void* dof = mapped(const_cast<uint64_t*>(offsets), (size_t)n * 8);
         const void* dln = dof ? mapped(const_cast<uint32_t*>(lengths), (size_t)n * 4) : nullptr;
         if (dln && is_pinned(frames, 1)) {
-            const framesum::plan::Scan sc =
-                framesum::plan::scan_from(scan_descriptors(offsets, lengths, n), offsets, lengths, n, frames_bytes);
-            if (sc.bad < n)
-                return set_err(ctx, FS_E_INVALID, "fs_digest_batch_host: frame " + std::to_string(sc.bad) + " ends past frames_bytes");
+            const framesum::plan::Scan sc = scan_host(ctx, offsets, lengths, n, frames_bytes);
+            if (sc.bad < n) return FS_E_INVALID;
             const void* df = sc.hi > sc.lo ? mapped(const_cast<uint8_t*>(frames + sc.lo), sc.hi - sc.lo) : nullptr;
-            if (df && host_force(ctx, sc.max_len, sc.min_len) == framesum::kForceSmallExact &&
+            if (df && framesum::host_force(ctx->force_kernel, sc.max_len, sc.min_len) == framesum::kForceSmallExact &&
                 (reinterpret_cast<uintptr_t>(frames) & 3u) == 0u)
                 return host_inplace(ctx, static_cast<const uint8_t*>(df) - sc.lo, static_cast<const uint64_t*>(dof),
                                     static_cast<const uint32_t*>(dln), n, mtu, out, status);
@@ -568,22 +560,19 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
             FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->d_desc, src_off, (size_t)n * 8, hipMemcpyHostToDevice, ks));
             FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->d_desc + (size_t)n * 8, src_len, (size_t)n * 4, hipMemcpyHostToDevice, ks));
         }
-        const framesum::plan::Scan sc =
-            framesum::plan::scan_from(scan_descriptors(offsets, lengths, n), offsets, lengths, n, frames_bytes);
+        const framesum::plan::Scan sc = scan_host(ctx, offsets, lengths, n, frames_bytes);
         if (sc.bad < n) {
             drain_host_streams(ctx);  // the descriptor copy reads the caller's arrays: done before returning
-            return set_err(ctx, FS_E_INVALID, "fs_digest_batch_host: frame " + std::to_string(sc.bad) + " ends past frames_bytes");
+            return FS_E_INVALID;
         }
-        const int force = host_force(ctx, sc.max_len, sc.min_len);
+        const int force = framesum::host_force(ctx->force_kernel, sc.max_len, sc.min_len);
         if (sc.hi - sc.lo <= kChunkBytes)
             return host_single(ctx, frames, frames_bytes, offsets, lengths, n, mtu, out, status, sc, force);
         FS_HIP(ctx, hipStreamSynchronize(ks));  // (the chunked path below stages the descriptors itself)
     }
-    const framesum::plan::Scan sc =
-        framesum::plan::scan_from(scan_descriptors(offsets, lengths, n), offsets, lengths, n, frames_bytes);
-    if (sc.bad < n)
-        return set_err(ctx, FS_E_INVALID, "fs_digest_batch_host: frame " + std::to_string(sc.bad) + " ends past frames_bytes");
-    const int force = host_force(ctx, sc.max_len, sc.min_len);
+    const framesum::plan::Scan sc = scan_host(ctx, offsets, lengths, n, frames_bytes);
+    if (sc.bad < n) return FS_E_INVALID;
+    const int force = framesum::host_force(ctx->force_kernel, sc.max_len, sc.min_len);
     ctx->host_dirty = true;  // until this call has waited for all of its work
     ctx->last_host_path = 3;
     pst = ensure_pinned(ctx, n);
@@ -676,9 +665,8 @@ fs_status fs_fill_batch_host(fs_ctx* ctx, uint8_t* frames, uint64_t frames_bytes
     ctx->err.clear();
     if (flags & ~(uint32_t)(FS_FILL_CSUM | FS_FCS_APPEND))
         return set_err(ctx, FS_E_INVALID, "fs_fill_batch_host: unknown flags");
-    if (n == 0) return FS_SUCCESS;
-    if (n > kMaxFrames) return set_err(ctx, FS_E_INVALID, "fs_fill_batch_host: n too large (at most 2^31 frames per call)");
-    if (!frames || !offsets || !lengths || !out) return set_err(ctx, FS_E_INVALID, "fs_fill_batch_host: null pointer");
+    const fs_status ast = check_batch(ctx, "fs_fill_batch_host", frames, offsets, lengths, n, out, false);
+    if (n == 0 || ast != FS_SUCCESS) return ast;
     // One staged span [lo, hi) (the frames and, with FS_FCS_APPEND, their FCS bytes), copied in,
     // filled, copied back. Not chunk-pipelined: written spans of unordered batches may interleave.
     const uint32_t extra = (flags & FS_FCS_APPEND) ? 4u : 0u;
@@ -852,7 +840,7 @@ fs_status fs_ctx_set_kernel(fs_ctx* ctx, int variant) {
 
 int fs_ctx_last_kernel(const fs_ctx* ctx) {
     if (!ctx || !ctx->h_report) return FS_E_INVALID;
-    return (int)ctx->h_report[framesum::kReportChosen];
+    return (int)ctx->choice.chosen;
 }
 
 #ifdef FS_TEST_HOOKS
@@ -862,7 +850,7 @@ fs_status fs_test_set_fault(fs_ctx* ctx, long chunk) {
     ctx->fault_chunk = chunk;
     return FS_SUCCESS;
 }
-// ... and the context's kernel choice set to any launch_digest force value, e.g. kForceSmallExact (16):
+// ... and the context's kernel choice set to any choose() force value (framesum_choice.h), e.g. kForceSmallExact (16):
 // the small-frame kernel for every launch, whatever the reports say (the parity suite's
 // "small_exact" column runs every case through that kernel's own long-frame path).
 fs_status fs_test_set_kernel_exact(fs_ctx* ctx, int force) {

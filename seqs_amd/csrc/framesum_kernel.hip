@@ -1165,7 +1165,7 @@ __device__ __forceinline__ void post_report(uint64_t report, uint32_t bits = 0u)
 // Bit 47 of `report`: the host is counting short launches (or a long report is news to it), so every
 // wave reports its long tiles; otherwise only the grid's first wave does, in its "ran" post (uniform
 // long traffic then costs one post per launch, not one per tile).
-__device__ __forceinline__ bool report_watch(uint64_t report) { return ((report >> 47) & 1u) != 0u; }
+__device__ __forceinline__ bool report_watch(uint64_t report) { return (report & kReportWatch) != 0u; }
 
 // A wave's posts for a tile of frames of `len` (group-uniform; 0 for an empty group), issued at the
 // tile's start, after its row prefetch. A store to host memory counts in vmcnt until it lands (~PCIe
@@ -2253,144 +2253,33 @@ extern "C" int fs_debug_read_stamps(void* host, size_t bytes) {
 
 hipError_t launch_digest(const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
                          uint32_t mtu, const FsTables* tables, void* out, uint8_t* status, hipStream_t stream,
-                         int num_cus, volatile uint32_t* report_host, uint32_t* report_dev, uint32_t* next_id,
+                         int num_cus, ChoiceState& state, const volatile uint32_t* report_host, uint32_t* report_dev,
                          int force, FsOp op, uint8_t* wframes, uint32_t tx) {
-    if (n == 0) return hipSuccess;
+    if (n == 0) return hipSuccess;  // (an empty batch takes no launch sequence number)
     const uint32_t max_blocks = (uint32_t)(num_cus > 0 ? num_cus : 256);
-    // The report of the launches before (the latest launch id that met a mixed-length tile):
-    // launches are enqueued ahead of the GPU, so a report arrives several launches late; the
-    // mixed kernel stays chosen for kStickyLaunches launches after the latest report (it keeps
-    // reporting while the traffic is mixed, on every kMixedSample-th launch). A heuristic only:
-    // never a result.
-    // Launch ids are 16-bit (they travel in the report pointer's top bits; 0 = never reported).
-    // The window is timed on the host instead: `next_id` is the context's 32-bit launch sequence,
-    // and the host notes the sequence at which it first saw the report word change (host-only
-    // words kReportSeen / kReportSeenSeq), so a report stays recent for kStickyLaunches of this
-    // context's launches and never aliases an old one after the 16-bit ids wrap.
-    constexpr uint32_t kStickyLaunches = 4096;
-    // (the counter is the context's: another context's launches never shift this one's window;
-    // a context is used from one thread at a time, include/framesum.h)
-    const uint32_t seq = (*next_id)++;
-    uint32_t id = seq & 0xFFFFu;
-    if (id == 0u) id = 0x8000u;  // (0 means "never reported"; any non-zero tag will do)
     const uint64_t rdev = reinterpret_cast<uint64_t>(report_dev);
     const bool can_report = report_host && rdev != 0u && (rdev & ~kReportAddrMask) == 0u;  // (64-B aligned too)
-    uint64_t report = can_report ? rdev | ((uint64_t)id << 48) : 0u;
-    bool mixed = false, giant = false;
-    if (can_report) {
-        const uint32_t latest = report_host[kReportLatest];
-        giant = (latest & kReportMixedGiant) != 0u;
-        if (latest != report_host[kReportSeen]) {
-            report_host[kReportSeen] = latest;
-            report_host[kReportSeenSeq] = seq;
-        }
-        mixed = latest != 0u && seq - report_host[kReportSeenSeq] <= kStickyLaunches;
-        // the mixed-length kernel's own posts only refresh the window: sampled (kMixedSample)
-        if (latest == 0u || seq % kMixedSample == 0u) report |= kAskMixed;
-        // A context's first launches run the mixed-length kernel: it reports its own mode-B tiles,
-        // so mixed traffic keeps it from the first batch on (the one-pass kernel's report would
-        // arrive launches late, after slow first batches), and uniform traffic moves to the
-        // one-pass kernel once the window ends (host-only word: the device never writes it).
-        const uint32_t left = report_host[kReportInitial];
-        if (left != 0u) {
-            report_host[kReportInitial] = left - 1u;
-            mixed = true;
-        }
-    }
-    // fs_ctx_set_kernel: 2 the mixed-length kernel (digest_kernel_ab, pieces), 4 the one-pass kernel, 3 the
-    // segment kernel (digest_kernel_g: another mixed-length decomposition, slower on C3)
-    if (force == 2 || force == 3 || force == 4) mixed = force != 4;
-    if (force == kForceUniformHost) mixed = false;
-    // the automatic choice runs the segment kernel while the latest mixed report saw a giant tile
-    const bool segments = force == 3 || (mixed && giant && (force == 0 || force == kForceNoSmall || force == 8));
-    // The small-frame kernel (RX digest and FCS verify; a TX fill keeps the 4-lane choice above).
-    // The kernels report launches that met a frame longer than kSmallMaxLen (kReportLong), and the
-    // 4-lane kernels, when asked (kAskRan), that a launch ran (kReportRan, with the grid's first
-    // tile's own long flag in the same word, kReportRanLong); the host counts the launches it sees
-    // run since the latest long report. Variant 0
-    // moves to the small-frame kernel after kShortLaunchesAuto of them; variant 8 runs it until a
-    // long report arrives, then the 4-lane choice until kShortLaunchesSmall launches ran short
-    // again. The reports come launches late, so a long frame can still meet the small-frame kernel:
-    // it stays correct there, only slower (one lane streams it). kForceSmallExact: the host-staged
-    // path, which has seen every length.
-    bool small = false;
-    // kForceNoSmall (a host-staged batch with a long frame) reports as the automatic choice does, so
-    // its long frames end a short streak; it only never picks the small-frame kernel itself
-    const bool autov = force == 0 || force == kForceNoSmall || force == kForceUniformHost;
-    if (can_report) {
-        const uint32_t lng = report_host[kReportLong], rw = report_host[kReportRan], ran = rw & 0xFFFFu;
-        const bool ran_new = ran != report_host[kReportRanSeen];
-        if (lng != report_host[kReportLongSeen] || (ran_new && (rw & kReportRanLong) != 0u)) {
-            report_host[kReportLongSeen] = lng;
-            report_host[kReportShort] = 0u;
-            report_host[kReportLongEver] = 1u;
-        } else if (ran_new && ran != lng && report_host[kReportShort] < (1u << 30)) {
-            report_host[kReportShort] = report_host[kReportShort] + 1u;
-        }
-        report_host[kReportRanSeen] = ran;
-        const uint32_t streak = report_host[kReportShort];
-        if (force == 0) small = streak >= kShortLaunchesAuto;
-        if (force == 8) small = report_host[kReportLongEver] == 0u || streak >= kShortLaunchesSmall;
-        // every workgroup reports its long frames while the host counts short launches
-        if ((autov || force == 8) && streak > 0u) report |= 1ull << 47;
-        // "ran": variant 0 samples it on long traffic and asks every launch while it counts short
-        // ones; variant 8 (short traffic expected: back to the small-frame kernel after 2 short
-        // launches) asks every launch
-        if (force == 8 || (autov && (streak > 0u || seq % kRanSample == 0u))) report |= kAskRan;
-    } else if (force == 8) {
-        small = true;  // no report block: the caller's choice as it stands
-    }
-    if (force == kForceSmallExact) small = true;
-    if (force == kForceNoSmall || force == kForceUniformHost || op == FsOp::kFill) small = false;
-    if (small) mixed = false;
-    // the variant this launch runs, for fs_ctx_last_kernel (host-only word)
-    auto chosen = [&](uint32_t v) {
-        if (report_host) report_host[kReportChosen] = v;
-    };
-    // Fewer frames per tile (8, then 4) while 16 would leave waves without a tile: a small
-    // batch still spreads over every CU. The groups past a tile's frames stay empty in the
-    // one-pass kernel; the mixed-length kernel gives them pieces of the tile's long frames.
-    uint32_t fpt = kFramesPerTile;
-    const uint32_t waves = max_blocks * (uint32_t)kWavesPerBlock;
-    while (fpt > 4u && (n + fpt - 1) / fpt < waves) fpt >>= 1;
-    const uint32_t tiles = (n + fpt - 1) / fpt;
-    uint32_t blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks > max_blocks) blocks = max_blocks;
+    Reports r{};
+    if (can_report) r = Reports{report_host[kReportLatest], report_host[kReportLong], report_host[kReportRan]};
+    const Choice c = choose(state, can_report ? &r : nullptr, force, op == FsOp::kFill);
+    const uint64_t report = can_report ? rdev | ((uint64_t)c.id << 48) | c.bits : 0u;
     uint2* o = reinterpret_cast<uint2*>(out);
-#define FS_LAUNCH(K)                                                                                        \
-    hipLaunchKernelGGL(K, dim3(blocks), dim3(kThreads), 0, stream, frames, offsets, lengths, n, mtu, \
-                       tables, o, status, report, wframes, tx, fpt)
-    chosen(small ? 8u : mixed ? (segments ? 3u : 2u) : 4u);
-    if (small) {
-        const uint32_t stiles = (n + 63u) / 64u;  // 64 frames (one per lane) per wave
-        uint32_t sb = (stiles + kSmallWaves - 1u) / kSmallWaves;
-        if (sb > 2u * max_blocks) sb = 2u * max_blocks;
-        if (op == FsOp::kFcs)
-            hipLaunchKernelGGL((digest_kernel_s<kOpsFcs>), dim3(sb), dim3(kWave * kSmallWaves), 0, stream, frames,
-                               offsets, lengths, n, mtu, tables, reinterpret_cast<uint2*>(out), status, report);
-        else
-            hipLaunchKernelGGL((digest_kernel_s<kOpsDigest>), dim3(sb), dim3(kWave * kSmallWaves), 0, stream, frames,
-                               offsets, lengths, n, mtu, tables, reinterpret_cast<uint2*>(out), status, report);
+    if (c.variant == (uint32_t)kKernelSmall) {  // (never a fill: choose())
+        const auto kernel = op == FsOp::kFcs ? digest_kernel_s<kOpsFcs> : digest_kernel_s<kOpsDigest>;
+        hipLaunchKernelGGL(kernel, dim3(grid_small(n, max_blocks, kSmallWaves)), dim3(kWave * kSmallWaves), 0, stream,
+                           frames, offsets, lengths, n, mtu, tables, o, status, report);
         return hipGetLastError();
     }
-    switch (op) {
-    case FsOp::kDigest:
-        if (mixed && segments) FS_LAUNCH((digest_kernel_g<kOpsDigest>));
-        else if (mixed) FS_LAUNCH((digest_kernel_ab<kOpsDigest>));
-        else FS_LAUNCH((digest_kernel_a<kOpsDigest>));
-        break;
-    case FsOp::kFill:
-        if (mixed && segments) FS_LAUNCH((digest_kernel_g<kOpsTx>));
-        else if (mixed) FS_LAUNCH((digest_kernel_ab<kOpsTx>));
-        else FS_LAUNCH((digest_kernel_a<kOpsTx>));
-        break;
-    case FsOp::kFcs:
-        if (mixed && segments) FS_LAUNCH((digest_kernel_g<kOpsFcs>));
-        else if (mixed) FS_LAUNCH((digest_kernel_ab<kOpsFcs>));
-        else FS_LAUNCH((digest_kernel_a<kOpsFcs>));
-        break;
-    }
-#undef FS_LAUNCH
+    // the 4-lane kernels, [op][segment, mixed-length, one-pass]
+    static_assert((int)FsOp::kDigest == kOpsDigest && (int)FsOp::kFill == kOpsTx && (int)FsOp::kFcs == kOpsFcs, "row = op");
+    static const decltype(&digest_kernel_a<kOpsDigest>) kernels[3][3] = {
+        {digest_kernel_g<kOpsDigest>, digest_kernel_ab<kOpsDigest>, digest_kernel_a<kOpsDigest>},
+        {digest_kernel_g<kOpsTx>, digest_kernel_ab<kOpsTx>, digest_kernel_a<kOpsTx>},
+        {digest_kernel_g<kOpsFcs>, digest_kernel_ab<kOpsFcs>, digest_kernel_a<kOpsFcs>}};
+    const int col = c.variant == (uint32_t)kKernelSegment ? 0 : c.variant == (uint32_t)kKernelMixed ? 1 : 2;
+    const Grid g = grid_4lane(n, max_blocks, kWavesPerBlock, kFramesPerTile);
+    hipLaunchKernelGGL(kernels[(int)op][col], dim3(g.blocks), dim3(kThreads), 0, stream, frames, offsets, lengths, n,
+                       mtu, tables, o, status, report, wframes, tx, g.fpt);
     return hipGetLastError();
 }
 

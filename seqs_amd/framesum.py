@@ -235,6 +235,8 @@ class Engine:
         launch reports a frame over 128 B, then the automatic choice until short traffic resumes.
         The automatic choice itself moves to the small-frame kernel after 16 launches seen to run
         with no frame over 128 B (include/framesum.h). A TX fill never runs the small-frame kernel.
+        A host-staged batch, with 0 or 8, runs the small-frame kernel when its frames are all <= 128 B
+        and the one-pass kernel from the context's first call when its lengths all lie within 256 B.
         Any other value raises."""
         self._check(self.lib.fs_ctx_set_kernel(self._ctx, int(variant)), "fs_ctx_set_kernel")
 
