@@ -187,8 +187,15 @@ __device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xffu) <<
 // One's-complement accumulation: v_sad_u16(x, 0, acc) = acc + x[15:0] + x[31:16] in ONE op.
 // x[15:0] + x[31:16] is congruent to the dword's native little-endian value mod 65535 and
 // is 0 iff the dword is 0, which is all Sum16's fold needs. It is linear
-// over disjoint byte masks (no carry crosses a byte). A lane adds at most 2^15 dwords of a
-// frame under 512 KiB, each < 2^17, so the 32-bit accumulator cannot wrap there.
+// over disjoint byte masks (no carry crosses a byte). Each term is at most 2 * 65535, so a 32-bit
+// accumulator holds any 2^15 of them (2^15 * 131070 = 2^32 - 65536) but not 2^15 + 1 saturated
+// ones. The 4-lane kernels give a lane 4 of every 16 consecutive dwords: at most 2^15 of a frame
+// of up to 2^17 dwords. A frame under 512 KiB touches 2^17 + 1 dwords when sa + len > 2^19; the
+// lane that then adds 2^15 + 1 of them holds the frame's first and last dword, which together
+// hold len - 4 (2^17 - 1) <= 3 frame bytes (< 2 * 65535), so it stays below 2^32 too: the
+// recompute gate of finish_l4 (len >= 2^19) covers every 4-lane accumulator. Sums one lane makes
+// over unbounded ranges (global_sum, the small-frame kernel's long-frame loop) do not rely on this:
+// they use 64 bits or fold (tests/kernel_model.py: l4_checksum_model restates all of it).
 __device__ __forceinline__ uint32_t sad16(uint32_t x, uint32_t acc) { return __builtin_amdgcn_sad_u16(x, 0u, acc); }
 
 // bytes of absolute dword k that lie in the absolute byte range [a0, a1)
@@ -329,12 +336,14 @@ __device__ __forceinline__ uint32_t slot_sum(const char* lds, uint32_t hw, uint3
 // (through a global-address-space pointer: inside the out-of-line parse a plain pointer argument
 // is generic, and a flat load there made hipcc's wait counting fall back to vmcnt(0))
 typedef __attribute__((address_space(1))) const uint32_t gcu32;
-__device__ __forceinline__ uint32_t global_sum(const uint32_t* fb, uint32_t sa, int p0, int p1) {
-    uint32_t s = 0;
+// (64 bits: the Ethernet padding of a frame can be any length, and 2^15 + 1 saturated dwords
+// already exceed 32 bits -- a wrap would move the checksum by one, 2^32 = 1 mod 65535)
+__device__ __forceinline__ uint64_t global_sum(const uint32_t* fb, uint32_t sa, int p0, int p1) {
+    uint64_t s = 0;
     if (p1 <= p0) return s;
     const int a0 = (int)sa + p0, a1 = (int)sa + p1;
     gcu32* gfb = reinterpret_cast<gcu32*>(reinterpret_cast<uintptr_t>(fb));
-    for (int k = a0 >> 2; k <= (a1 - 1) >> 2; ++k) s = sad16(gfb[k] & range_mask(k, a0, a1), s);
+    for (int k = a0 >> 2; k <= (a1 - 1) >> 2; ++k) s += sad16(gfb[k] & range_mask(k, a0, a1), 0u);
     return s;
 }
 
@@ -491,7 +500,7 @@ __device__ __attribute__((noinline)) void parse_tile(uint32_t hw, uint32_t grp, 
     // longer IP headers are summed from global memory)
     const uint32_t h1 = min(off, len);
     uint32_t hsum = slot_sum(lds, hw, grp, gl, sa, 0, (int)h1, min(5, kSlotDw / 4), xo);
-    if (kSlotDw < 32 && sa + h1 > 4u * kSlotDw) hsum = global_sum(fbs, sa, 0, (int)h1);
+    if (kSlotDw < 32 && sa + h1 > 4u * kSlotDw) hsum = (uint32_t)global_sum(fbs, sa, 0, (int)h1);  // (< 80 bytes)
     const bool pad_in_slot = sa + len <= 4u * kSlotDw;
     int64_t pad = -1;
     if (__ballot(len >= 34u && end < len && pad_in_slot) != 0) {
@@ -511,7 +520,8 @@ __device__ __forceinline__ uint32_t finish_l4(const uint32_t* fb, uint32_t sa, u
     int64_t t = (int64_t)main_sum + P.corr + 65535LL * (1LL << 20);
     if (len >= (1u << 19)) {
         // >= 512 KiB frame (only reachable with a huge Ethernet padding): a lane's streamed
-        // 32-bit sum may have wrapped, so sum the L4 segment [off, end) exactly from memory.
+        // 32-bit sum may have wrapped (it cannot in a shorter frame: see sad16), so sum the L4
+        // segment [off, end), under 64 KiB, exactly from memory.
         t = (int64_t)global_sum(fb, sa, (int)P.off, (int)P.end) + P.corr_fixed + 65535LL * (1LL << 20);
     }
     uint64_t x = (uint64_t)t;
@@ -2204,6 +2214,9 @@ digest_kernel_s(const uint8_t* __restrict__ frames, const uint64_t* __restrict__
         // a frame longer than the slot: its remaining 16-B chunks from memory, 4 in flight (correct
         // for any length, but one lane streams the frame: the variant is for short frames)
         for (uint32_t c = kSmallSlotRows; c < (lim ? nch : 0u); c += 4u) {
+            // this one lane adds the whole frame: folded mod 65535 once per iteration (16 dwords,
+            // < 2^21), the sum stays below 2^22 for any length (the finish needs it mod 65535 only)
+            cs = (cs & 0xffffu) + (cs >> 16);
             u32x4 u[4];
 #pragma unroll
             for (uint32_t i = 0; i < 4u; ++i)

@@ -46,7 +46,10 @@ def _fill_l4(frame: bytearray, corrupt: bool, rnd: random.Random) -> None:
 
 
 def valid_frame(rnd: random.Random, proto: int = 6, payload: int | None = None, ip_opts: int = 0,
-                tcp_opts: int = 0, pad: int = 0, corrupt: bool = False) -> bytes:
+                tcp_opts: int = 0, pad: int = 0, corrupt: bool = False, payload_bytes: bytes | None = None) -> bytes:
+    """`payload_bytes`: the L4 payload itself (its length is the payload length) instead of random bytes."""
+    if payload_bytes is not None:
+        payload = len(payload_bytes)
     if payload is None:
         payload = rnd.randrange(0, 1500)
     ihl = 5 + ip_opts
@@ -60,15 +63,19 @@ def valid_frame(rnd: random.Random, proto: int = 6, payload: int | None = None, 
         l4[12] = ((5 + tcp_opts) << 4) | (l4[12] & 0x0F)
     else:
         struct.pack_into(">H", l4, 4, 8 + payload)
+    if payload_bytes is not None:
+        l4[l4h:] = payload_bytes
     frame = eth + ip + l4 + bytearray(rnd.randbytes(pad))
     _fill_l4(frame, corrupt, rnd)
     return bytes(frame)
 
 
-def zero_sum_frame(rnd: random.Random, proto: int = 6) -> bytes:
-    """A valid frame whose computed L4 checksum is 0x0000 (the fold hits 0xFFFF)."""
+def zero_sum_frame(rnd: random.Random, proto: int = 6, payload: int | None = None) -> bytes:
+    """A valid frame whose computed L4 checksum is 0x0000 (the fold hits 0xFFFF). `payload`: the L4
+    payload length (even, >= 2; its last word is the one chosen); by default a random one under 400."""
+    assert payload is None or (payload >= 2 and payload % 2 == 0)
     for _ in range(200):
-        f = bytearray(valid_frame(rnd, proto, payload=rnd.randrange(2, 400) & ~1))
+        f = bytearray(valid_frame(rnd, proto, payload=(rnd.randrange(2, 400) & ~1) if payload is None else payload))
         ihl = f[14] & 0xF
         off = 14 + ihl * 4
         pos = off + (16 if proto == 6 else 6)

@@ -7,7 +7,8 @@ also removes the <=3 zero bytes of the dword rounding, the 4-byte init trick,
 and the native-domain (little-endian dword) one's-complement sum streamed from
 frame dword 10 with exact head/padding corrections — so the algebra can be
 checked on CPU against zlib / the oracle before and independently of the GPU.
-Small inputs only.
+Small inputs only (the CRC models; the accumulator model at the end of the file
+is vectorised and takes frames of 512 KiB).
 """
 from __future__ import annotations
 
@@ -344,3 +345,160 @@ def crc32_tile_segments(buf: bytes, frames: list[tuple[int, int]], base_phase: i
         t = (4 - ((f["S"] + f["ln"]) & 3)) & 3
         out.append(apply(ZFIN[t], Y) ^ 0xFFFFFFFF)
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# The one's-complement sum as the kernels accumulate it: v_sad_u16 terms (lo16 + hi16 of every
+# frame dword, head and tail bytes masked) added into 32-bit accumulators, the mod-65535 folds,
+# the corrections and finish_l4's fold. Every accumulator is computed exactly (Python / uint64) and
+# reported beside the value the 32-bit register would hold, so a test can assert both the result
+# and that nothing reached 2^32 on the way.
+
+M32 = 1 << 32
+GATE_LEN = 1 << 19  # finish_l4 recomputes [off, end) from memory for frames this long
+SMALL_SLOT_DWORDS = 36  # the small-frame kernel's slot (kSmallSlotRows chunks of 4 dwords)
+
+
+def fold16(x: int) -> int:
+    """One fold step, as the kernels apply it to a 32-bit register."""
+    return (x & 0xFFFF) + (x >> 16)
+
+
+def bswap16(w: int) -> int:
+    return ((w & 0xFF) << 8) | (w >> 8)
+
+
+def sad_terms(buf: bytes, S: int, length: int):
+    """The v_sad_u16 term of every dword the frame buf[S:S+length] touches (numpy uint64, ndall
+    entries): lo16 + hi16 of the dword with the bytes outside the frame masked off."""
+    import numpy as np
+
+    sa = S & 3
+    nd = (sa + length + 3) >> 2
+    raw = np.zeros(4 * nd, dtype=np.uint8)
+    raw[sa : sa + length] = np.frombuffer(buf, dtype=np.uint8, count=length, offset=S)
+    h = raw.view("<u2").astype(np.uint64)
+    return h[0::2] + h[1::2]
+
+
+def half_sum(buf: bytes, S: int, p0: int, p1: int) -> int:
+    """Exact sum of frame bytes [p0, p1) in the accumulators' domain: a byte at absolute address a
+    weighs 256^(a & 1). This is what the fixed global_sum returns (a 64-bit accumulator)."""
+    import numpy as np
+
+    if p1 <= p0:
+        return 0
+    b = np.frombuffer(buf, dtype=np.uint8, count=p1 - p0, offset=S + p0).astype(np.uint64)
+    odd = (S + p0) & 1
+    return int(b[odd::2].sum()) + 256 * int(b[1 - odd :: 2].sum())
+
+
+def lane_sums(terms, pos0: int, cuts=()):
+    """The 4-lane kernels' accumulators. Frame dword x sits at row position (pos0 + x) mod 16 and
+    lane ((pos0 + x) mod 16) // 4 adds it. Block-aligned rows (one-pass and segment kernels):
+    pos0 = the 64-B block phase of frame dword 0. End-anchored rows (the mixed-length kernel's
+    mode A): pos0 = -nd mod 16, so that the last row ends with the frame's last dword.
+    `cuts`: rows (from the frame's first row) before which a segment ends (the segment kernel parks
+    and restarts its accumulators there). Returns one [4 exact lane sums] per segment."""
+    import numpy as np
+
+    nd = len(terms)
+    rows = (pos0 + nd + 15) // 16
+    grid = np.zeros(16 * rows, dtype=np.uint64)
+    grid[pos0 : pos0 + nd] = terms
+    grid = grid.reshape(rows, 16)
+    out, r0 = [], 0
+    for r1 in list(cuts) + [rows]:
+        if r1 > r0:
+            out.append([int(v) for v in grid[r0:r1].sum(axis=0).reshape(4, 4).sum(axis=1)])
+        r0 = max(r0, r1)
+    return out
+
+
+def lane_dwords(nd: int, pos0: int):
+    """Frame dwords each of the 4 lanes adds (block-aligned or end-anchored rows, see lane_sums)."""
+    def at(p):  # the k in [pos0, pos0 + nd) with k = p mod 16
+        return (pos0 + nd - 1 - p) // 16 - (pos0 - 1 - p) // 16
+
+    return [sum(at(p) for p in range(4 * l, 4 * l + 4)) for l in range(4)]
+
+
+def small_lane_sum(terms, xo: int, fixed: bool = True):
+    """The small-frame kernel's single accumulator: the dwords in the slot (frame dwords
+    [0, 36 - xo), xo = frame dword 0's place in its 16-B chunk) added plainly, then 4 chunks (16
+    dwords, the first at slot dword 36) per iteration of the beyond-the-slot loop, the accumulator
+    folded once before each iteration (`fixed`; the kernel before the fix did not fold).
+    Returns (the register's final value, the largest exact value it would have needed to hold)."""
+    nd = len(terms)
+    lim1 = min(nd, SMALL_SLOT_DWORDS - xo)
+    cs = int(terms[:lim1].sum())
+    peak = cs
+    x = lim1
+    while x < nd:
+        if fixed:
+            cs = fold16(cs)
+        cs += int(terms[x : x + 16].sum())
+        peak = max(peak, cs)
+        if not fixed:
+            cs %= M32
+        x += 16
+    return cs % M32, peak
+
+
+def l4_checksum_model(buf: bytes, S: int, length: int, kernel: str, ph: int = 0, cuts=(), fixed: bool = True,
+                      gate_len: int = GATE_LEN):
+    """The L4 checksum of the valid-shaped TCP/UDP frame buf[S:S+length] as `kernel` computes it
+    ("one_pass", "mixed", "segments", "small"), with every 32-bit accumulator on the way.
+    `ph`: block phase of frame dword 0 (block-aligned kernels) or its place in its 16-B chunk
+    (small kernel); `cuts`: see lane_sums; `fixed=False` models the kernels before the padding sum
+    became exact and the small kernel folded in its long-frame loop.
+    Returns (checksum, [exact value of every 32-bit accumulator that fed it])."""
+    f = buf[S : S + length]
+    sa = S & 3
+    ihl = f[14] & 0xF
+    off = 14 + 4 * ihl
+    tl = struct.unpack(">H", f[16:18])[0]
+    end = (14 + tl) & 0xFFFF
+    proto = f[23]
+    assert proto in (6, 17) and off <= end <= length
+    parity = (sa + off) & 1
+
+    def wt(w):  # a big-endian word at an even frame offset, in the accumulators' domain
+        return w if parity else bswap16(w)
+
+    be = lambda p: struct.unpack(">H", f[p : p + 2])[0]  # noqa: E731
+    stored = be(off + (16 if proto == 6 else 6))
+    lenword = ((tl - 4 * ihl) & 0xFFFF) if proto == 6 else be(off + 4)
+    corr_fixed = -wt(stored) - (wt(be(off + 18)) if proto == 6 else 0)
+    corr_fixed += sum(wt(w) for w in (be(26), be(28), be(30), be(32), proto, lenword))
+    accs = []
+    hsum = half_sum(buf, S, 0, off)
+    pad = half_sum(buf, S, end, length)  # from the slot when it lies there, else global_sum
+    if not fixed:
+        accs.append(pad)
+        pad %= M32
+    terms = sad_terms(buf, S, length)
+    nd = len(terms)
+    if length >= gate_len:
+        main = half_sum(buf, S, off, end)  # at most 16,384 dwords: exact in 32 bits too
+        t = main + corr_fixed
+    else:
+        if kernel == "small":
+            main, peak = small_lane_sum(terms, ph & 3, fixed)
+            accs.append(peak)
+        else:
+            pos0 = (-nd) % 16 if kernel == "mixed" else ph
+            segs = lane_sums(terms, pos0, cuts if kernel == "segments" else ())
+            main = 0
+            for lanes in segs:
+                accs += lanes
+                main += sum(fold16(v % M32) for v in lanes)  # each lane folded, then the group's sum
+            accs.append(main)
+        t = main + corr_fixed - hsum - pad
+    t += 65535 << 20
+    assert 0 < t < 1 << 63
+    x = (t & 0xFFFFFFFF) + (t >> 32)
+    while x >> 16:
+        x = fold16(x)
+    l4 = ~x & 0xFFFF
+    return (l4 if parity else bswap16(l4)), accs
