@@ -228,6 +228,75 @@ func (g *GPU) FillBatch(frames [][]byte, mtu uint16, appendFCS bool, out []Diges
 	return nil
 }
 
+// Send is one send of SegmentBatch: a header template (54 bytes Ethernet + IPv4 + TCP, or 42
+// bytes Ethernet + IPv4 + UDP, as PutHeaders writes them) and the payload it carries.
+type Send struct {
+	Header  []byte
+	Payload []byte
+	MSS     uint16 // TCP payload bytes per frame; 0 = the whole payload in one frame (always 0 for UDP)
+}
+
+// SegmentBatch is the TX frame build for many sends at once: what TCPPacket.CalculateHeaders
+// (stacks/port_tcp.go:162-194), PutHeaders (port_tcp.go:95-106, port_udp.go:68-78) and the
+// payload cut of TCPConn.send do one segment at a time. Every send is cut into MSS-sized
+// segments; each gets its header (TotalLength, IPv4 ID stepped by prand16, Seq, FIN/PSH only on
+// the last segment), both checksums and, with appendFCS, its CRC-32 behind it. It returns, per
+// send, its finished frames (slices of one buffer).
+func (g *GPU) SegmentBatch(sends []Send, appendFCS bool) ([][][]byte, error) {
+	n := len(sends)
+	if n == 0 {
+		return nil, nil
+	}
+	var flags C.uint32_t
+	room := 0
+	if appendFCS {
+		flags, room = C.FS_FCS_APPEND, 4
+	}
+	cs := make([]C.fs_tx_send, n)
+	total := 0
+	for _, s := range sends {
+		total += len(s.Payload)
+	}
+	payload := make([]byte, total+1)
+	at := 0
+	for i, s := range sends {
+		if len(s.Header) != 54 && len(s.Header) != 42 {
+			return nil, errors.New("framesum: a header template is 54 bytes (TCP) or 42 bytes (UDP)")
+		}
+		copy(unsafe.Slice((*byte)(unsafe.Pointer(&cs[i].hdr[0])), 54), s.Header)
+		cs[i].mss = C.uint16_t(s.MSS)
+		cs[i].payload_off = C.uint64_t(at)
+		cs[i].payload_len = C.uint32_t(len(s.Payload))
+		at += copy(payload[at:], s.Payload)
+	}
+	var nFrames, nBytes C.uint64_t
+	if C.fs_segment_layout(&cs[0], C.uint32_t(n), flags, 1, &nFrames, &nBytes) != C.FS_SUCCESS {
+		return nil, errors.New("framesum: " + C.GoString(C.fs_last_error(nil)))
+	}
+	frames := make([]byte, int(nBytes)+1)
+	offs := make([]uint64, int(nFrames))
+	lens := make([]uint32, int(nFrames))
+	st := C.fs_segment_batch_host(g.ctx, &cs[0], C.uint32_t(n), (*C.uint8_t)(unsafe.Pointer(&payload[0])),
+		C.uint64_t(total), 0, flags, 1, (*C.uint8_t)(unsafe.Pointer(&frames[0])), C.uint64_t(nBytes),
+		(*C.uint64_t)(unsafe.Pointer(&offs[0])), (*C.uint32_t)(unsafe.Pointer(&lens[0])), nil, nil)
+	if st != C.FS_SUCCESS {
+		return nil, g.lastErr()
+	}
+	out := make([][][]byte, n)
+	f := 0
+	for i, s := range sends {
+		cnt := 1
+		if s.MSS != 0 && len(s.Payload) != 0 {
+			cnt = (len(s.Payload) + int(s.MSS) - 1) / int(s.MSS)
+		}
+		for k := 0; k < cnt; k++ {
+			out[i] = append(out[i], frames[offs[f]:offs[f]+uint64(lens[f])+uint64(room)])
+			f++
+		}
+	}
+	return out, nil
+}
+
 // GPUs is one host process's set of contexts, one per GPU, for NIC rings larger than one
 // PCIe link carries (fs_digest_batch_multi; BASELINE configs[4]).
 type GPUs struct {

@@ -141,6 +141,76 @@ fs_status fs_fill_batch_host(fs_ctx* ctx, uint8_t* frames, uint64_t frames_bytes
                              const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags, fs_digest* out,
                              uint8_t* status);
 
+/* TX frame build, device-resident: TCP segmentation and UDP frame build in one fused pass (what
+ * a NIC calls segmentation offload). The reference builds a TX frame in three steps that this
+ * call does for a whole batch: stacks/port_tcp.go:162-194 TCPPacket.CalculateHeaders derives the
+ * per-segment header fields, PutHeaders (port_tcp.go:95-106, port_udp.go:68-78) writes them in
+ * front of a payload slice, and TCPConn.send cuts that slice from the socket's ring.
+ *
+ * A send is a header template and a payload range. It makes S frames: 1 when mss is 0 or the
+ * payload is empty, else ceil(payload_len / mss); frame k carries payload bytes
+ * [k*mss, min(payload_len, (k+1)*mss)) of the range (its chunk). Frame k's header is the template
+ * with:
+ *   IPv4  byte 0 written as 0x45 (eth/headers.go:289-291), TotalLength = 20 + 20 (UDP: 8) + chunk,
+ *         ID = prand16 applied k times to the template's ID (port_tcp.go:173, :197-203: x ^= x<<7;
+ *         x ^= x>>9; x ^= x<<8 on uint16), Checksum = CalculateChecksum of the header as written;
+ *   TCP   Seq = template Seq + k*mss (mod 2^32), FIN and PSH cleared on every frame but the last (the
+ *         usual segmentation rule: an extension, the reference's flags come from its ControlBlock),
+ *         urgent pointer 0 (:189), Checksum = CalculateChecksumIPv4(&ip, nil, chunk);
+ *   UDP   Length = 8 + payload_len, Checksum = CalculateChecksumIPv4 (a computed 0 is written as 0).
+ * Every other header byte is copied. With FS_FCS_APPEND the frame's CRC-32 follows it little-endian.
+ * Both checksums are written into every frame whose RecvEth evaluation reaches the checksum compare,
+ * as FS_FILL_CSUM does; a frame RecvEth rejects earlier (a zero port, a frame above `mtu`, a
+ * TotalLength that wraps the reference's uint16 `end`) gets zero checksum fields and its verdict.
+ *
+ * Layout: frames lie in send order, then segment order; each starts at a multiple of `align` (a
+ * power of two, 1..4096) inside `frames` and owns a slot of round_up(len + (4 with FS_FCS_APPEND),
+ * align) bytes; fs_segment_layout gives the frame count and the sum of the slots. Bytes of `frames`
+ * that belong to no frame and no FCS are not written (not even read and written back).
+ * offsets[i] / lengths[i] (without FCS) describe frame i as fs_digest_batch takes them; out / status
+ * are what fs_digest_batch(..., mtu, ...) would report for it. Those four arrays may each be NULL.
+ *
+ * FS_E_INVALID, checked on the host before any device work (fs_segment_layout checks the same, less
+ * the payload range): a null ctx, sends or frames; align or flags out of range; reserved not 0;
+ * EtherType not 0x0800; IHL not 5; protocol not 6 or 17; TCP data offset not 5; UDP with mss not 0;
+ * a chunk above 65,495 (TCP) or 65,507 (UDP) bytes; S above FS_SEGMENT_MAX_FRAMES; a payload range
+ * outside payload_bytes; more than 2^31 frames; frames_bytes below the layout's. n_sends of 0 is
+ * success and writes nothing.
+ *
+ * `sends` is HOST memory, consumed before the call returns; payload, frames, offsets, lengths, out
+ * and status are DEVICE pointers. Asynchronous on `stream`. Calls on one context need no
+ * synchronization between them, on one stream or several: each call stages its sends in a block of
+ * its own that is reused only once its kernel has ended. fs_ctx_set_workgroups caps this kernel's
+ * grid too (uncapped, it launches two 12-wave workgroups per compute unit); fs_ctx_set_kernel and
+ * fs_ctx_last_kernel do not concern it. */
+#define FS_SEGMENT_MAX_FRAMES 4096u /* frames one send may produce */
+
+typedef struct fs_tx_send {  /* 72 bytes, no padding */
+    uint8_t hdr[54];      /* Ethernet 14 + IPv4 20 (IHL 5) + TCP 20 (data offset 5), wire order, as
+                             PutHeaders writes them. UDP: Ethernet + IPv4 + UDP 8 = the first 42 bytes */
+    uint16_t mss;         /* TCP payload bytes per frame; 0: the whole payload in one frame */
+    uint64_t payload_off; /* this send's payload = payload[payload_off : payload_off + payload_len) */
+    uint32_t payload_len;
+    uint32_t reserved;    /* must be 0 */
+} fs_tx_send;
+
+/* Host-only arithmetic: how many frames and how many bytes of `frames` a batch of sends needs. */
+fs_status fs_segment_layout(const fs_tx_send* sends, uint32_t n_sends, uint32_t flags, uint32_t align,
+                            uint64_t* n_frames, uint64_t* frames_bytes);
+
+fs_status fs_segment_batch(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_sends, const uint8_t* payload,
+                           uint64_t payload_bytes, uint32_t mtu, uint32_t flags, uint32_t align, uint8_t* frames,
+                           uint64_t frames_bytes, uint64_t* offsets, uint32_t* lengths, fs_digest* out,
+                           uint8_t* status, void* stream);
+
+/* fs_segment_batch with every pointer in HOST memory: copies the payload to the device, builds the
+ * frames, copies the frame span and the four arrays back (on the context's compute stream), and
+ * returns when they are written. The bytes between frames keep the caller's values. */
+fs_status fs_segment_batch_host(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_sends, const uint8_t* payload,
+                                uint64_t payload_bytes, uint32_t mtu, uint32_t flags, uint32_t align,
+                                uint8_t* frames, uint64_t frames_bytes, uint64_t* offsets, uint32_t* lengths,
+                                fs_digest* out, uint8_t* status);
+
 /* RX of raw wire frames that still carry their 4-byte FCS (NICs that do not strip it;
  * SURVEY.md §8f rank 4, not in the reference): lengths[i] includes the FCS. out/status are
  * fs_digest_batch's for frame[0:len-4), the bytes RecvEth would receive, except that status

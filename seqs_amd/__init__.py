@@ -10,6 +10,7 @@ from .framesum import (  # noqa: F401
     FCS_APPEND,
     FILL_CSUM,
     FS_ERR_FCS,
+    SEND_DTYPE,
     VERDICTS,
     Digest,
     Engine,
@@ -19,6 +20,7 @@ from .framesum import (  # noqa: F401
     lib_path,
     load_library,
     pack_frames,
+    segment_layout,
     shard_count,
     shard_slab_bytes,
     split_digests,
@@ -30,6 +32,7 @@ __all__ = [
     "FCS_APPEND",
     "FILL_CSUM",
     "FS_ERR_FCS",
+    "SEND_DTYPE",
     "VERDICTS",
     "Digest",
     "Engine",
@@ -39,6 +42,7 @@ __all__ = [
     "lib_path",
     "load_library",
     "pack_frames",
+    "segment_layout",
     "shard_count",
     "shard_slab_bytes",
     "split_digests",

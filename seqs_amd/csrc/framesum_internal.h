@@ -65,4 +65,23 @@ hipError_t launch_digest(const uint8_t* frames, const uint64_t* offsets, const u
 hipError_t launch_deinterleave(const uint8_t* gathered, uint32_t nshards, uint64_t n, void* out, uint8_t* status,
                                hipStream_t stream, uint64_t i0 = 0, uint64_t i1 = ~0ull);
 
+// ---- TX frame build (framesum_segment.hip). The kernel's CRC zero-shift tables Z_1, Z_2, Z_4, ...
+// Z_32768 (tables 0..15) and Z_12 (table 16) as their one-bit basis, basis[t][b][j] = Z_k[b][1 << j]:
+// every workgroup expands them into LDS.
+constexpr uint32_t kSegTableCount = 17, kSegTableZ12 = 16;
+struct SegTables {
+    uint32_t basis[kSegTableCount][4][8];
+};
+void build_segment_tables(SegTables* t);
+
+namespace segment {
+struct Block;
+}
+// One launch that builds the n_frames frames of a staged batch: `d_block` is the device copy of the
+// block segment::stage() filled (framesum_segment.h), `b` its layout. `workgroups` caps the grid.
+hipError_t launch_segment(const uint8_t* d_block, const segment::Block& b, uint32_t n_sends, uint32_t n_frames,
+                          const uint8_t* payload, uint8_t* frames, uint64_t* offsets, uint32_t* lengths, void* out,
+                          uint8_t* status, uint32_t mtu, uint32_t flags, uint32_t align, const SegTables* tables,
+                          int workgroups, hipStream_t stream);
+
 }  // namespace framesum

@@ -65,6 +65,9 @@ EXPORTED_SYMBOLS = (
     "fs_fill_batch",
     "fs_fill_batch_host",
     "fs_digest_batch_fcs",
+    "fs_segment_layout",
+    "fs_segment_batch",
+    "fs_segment_batch_host",
     "fs_digest_batch_multi",
     "fs_ctx_set_kernel",
     "fs_ctx_set_workgroups",
@@ -81,6 +84,10 @@ EXPORTED_SYMBOLS = (
 )
 
 DIGEST_DTYPE = np.dtype([("crc32", "<u4"), ("ip_csum", "<u2"), ("l4_csum", "<u2")])
+# fs_tx_send: one send of the TX frame build (72 bytes, no padding)
+SEND_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("payload_off", "<u8"), ("payload_len", "<u4"),
+                       ("reserved", "<u4")])
+SEGMENT_MAX_FRAMES = 4096
 
 
 class FramesumError(RuntimeError):
@@ -135,6 +142,12 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.fs_digest_batch_fcs.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp]
     lib.fs_digest_batch_fcs.restype = ctypes.c_int32
     lib.fs_ctx_set_kernel.argtypes = [vp, ctypes.c_int]
+    lib.fs_segment_layout.restype = i32
+    lib.fs_segment_layout.argtypes = [vp, u32, u32, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.fs_segment_batch.restype = i32
+    lib.fs_segment_batch.argtypes = [vp, vp, u32, vp, u64, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp]
+    lib.fs_segment_batch_host.restype = i32
+    lib.fs_segment_batch_host.argtypes = [vp, vp, u32, vp, u64, u32, u32, u32, vp, u64, vp, vp, vp, vp]
     if hasattr(lib, "fs_ctx_set_workgroups"):  # (absent from builds before round 4: same-box A/B runs)
         lib.fs_ctx_set_workgroups.restype = i32
         lib.fs_ctx_set_workgroups.argtypes = [vp, ctypes.c_int]
@@ -378,6 +391,90 @@ class Engine:
         self._check(st, "fs_deinterleave")
         return out, status
 
+    # ---- TX frame build -----------------------------------------------------
+    def segment_device(self, sends: np.ndarray, payload, mtu: int = 0, flags: int = 0, align: int = 4, stream=None,
+                       frames=None):
+        """Build the frames of `sends` (a SEND_DTYPE array on the host) from the uint8 CUDA tensor
+        `payload` (fs_segment_batch): TCP sends are cut into mss-sized segments, UDP sends make one
+        frame, headers, both checksums and (flags FCS_APPEND) the FCS are written in one pass.
+        `frames`: a uint8 CUDA tensor to build into (at least segment_layout's bytes; bytes between
+        frames are left as they are), else a new one. Returns (frames, offsets int64, lengths int32,
+        out (n, 2) int32, status uint8) device tensors; asynchronous on `stream`."""
+        import torch
+
+        sends = np.ascontiguousarray(sends, dtype=SEND_DTYPE)
+        n_frames, nbytes = segment_layout(sends, flags, align)
+        dev = payload.device
+        assert payload.is_cuda and payload.dtype == torch.uint8 and payload.is_contiguous()
+        if frames is None:
+            frames = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous()
+        offsets = torch.empty((n_frames,), dtype=torch.int64, device=dev)
+        lengths = torch.empty((n_frames,), dtype=torch.int32, device=dev)
+        out = torch.empty((n_frames, 2), dtype=torch.int32, device=dev)
+        status = torch.empty((n_frames,), dtype=torch.uint8, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        vp = ctypes.c_void_p
+        st = self.lib.fs_segment_batch(
+            self._ctx, sends.ctypes.data_as(vp), int(sends.size), vp(payload.data_ptr()), int(payload.numel()), mtu, flags,
+            align, vp(frames.data_ptr()), int(frames.numel()), vp(offsets.data_ptr()), vp(lengths.data_ptr()),
+            vp(out.data_ptr()), vp(status.data_ptr()), vp(stream.cuda_stream))
+        self._check(st, "fs_segment_batch")
+        return frames, offsets, lengths, out, status
+
+    def segment_host(self, sends: np.ndarray, payload: np.ndarray, mtu: int = 0, flags: int = 0, align: int = 4,
+                     frames: Optional[np.ndarray] = None):
+        """segment_device from and to host memory (fs_segment_batch_host). `frames`: a writable uint8
+        array to build into (pinned from host_empty, or pageable), else a new zeroed one. Returns
+        (frames, offsets uint64, lengths uint32, digests, status) numpy arrays."""
+        sends = np.ascontiguousarray(sends, dtype=SEND_DTYPE)
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        n_frames, nbytes = segment_layout(sends, flags, align)
+        if frames is None:
+            frames = np.zeros(nbytes, dtype=np.uint8)
+        assert frames.dtype == np.uint8 and frames.flags["C_CONTIGUOUS"] and frames.flags["WRITEABLE"]
+        offsets = np.zeros(n_frames, dtype=np.uint64)
+        lengths = np.zeros(n_frames, dtype=np.uint32)
+        out = np.zeros(n_frames, dtype=DIGEST_DTYPE)
+        status = np.zeros(n_frames, dtype=np.uint8)
+        vp = ctypes.c_void_p
+        st = self.lib.fs_segment_batch_host(
+            self._ctx, sends.ctypes.data_as(vp), int(sends.size), payload.ctypes.data_as(vp), payload.nbytes, mtu, flags,
+            align, frames.ctypes.data_as(vp), frames.nbytes, offsets.ctypes.data_as(vp), lengths.ctypes.data_as(vp),
+            out.ctypes.data_as(vp), status.ctypes.data_as(vp))
+        self._check(st, "fs_segment_batch_host")
+        return frames, offsets, lengths, out, status
+
+    def segment_batch(self, headers: Sequence[bytes], payloads: Sequence[bytes], mss: int,
+                      append_fcs: bool = False) -> list[list[bytes]]:
+        """The reference's TX frame build for many sends (stacks/port_tcp.go:162-194 CalculateHeaders +
+        PutHeaders + the payload cut of TCPConn.send): headers[i] is a 54-byte Ethernet + IPv4 + TCP
+        template (or 42 bytes for UDP, which makes one frame whatever `mss`), payloads[i] its send data.
+        Returns, per send, its finished frames (each with its FCS when `append_fcs`)."""
+        assert len(headers) == len(payloads)
+        sends = np.zeros(len(headers), dtype=SEND_DTYPE)
+        at = 0
+        for i, (h, p) in enumerate(zip(headers, payloads)):
+            assert len(h) in (42, 54), "a header template is 54 bytes (TCP) or 42 bytes (UDP)"
+            sends["hdr"][i, : len(h)] = np.frombuffer(bytes(h), dtype=np.uint8)
+            sends["mss"][i] = 0 if len(h) == 42 else mss
+            sends["payload_off"][i] = at
+            sends["payload_len"][i] = len(p)
+            at += len(p)
+        if len(sends) == 0:
+            return []
+        flags = FCS_APPEND if append_fcs else 0
+        payload = np.frombuffer(b"".join(bytes(p) for p in payloads) + b"\0", dtype=np.uint8)
+        frames, off, ln, _, _ = self.segment_host(sends, payload[:at], 0, flags, 1)
+        room = 4 if append_fcs else 0
+        res, f = [], 0
+        for s in sends:
+            cnt = send_frames(int(s["mss"]), int(s["payload_len"]))
+            res.append([bytes(frames[int(off[j]) : int(off[j]) + int(ln[j]) + room]) for j in range(f, f + cnt)])
+            f += cnt
+        return res
+
     # ---- host-staged path (numpy in, numpy out) -----------------------------
     def host_empty(self, shape, dtype=np.uint8) -> np.ndarray:
         """A numpy array in pinned host memory (fs_host_alloc), freed with the array."""
@@ -504,6 +601,24 @@ def digest_host_multi(engines: Sequence["Engine"], frames: np.ndarray, offsets: 
                          if (m := e.lib.fs_last_error(e._ctx).decode()))
         raise FramesumError(f"fs_digest_batch_multi failed ({st}): {msgs}")
     return out, status
+
+def send_frames(mss: int, payload_len: int) -> int:
+    """Frames one send makes: 1 when mss is 0 or the payload is empty, else ceil(payload_len / mss)."""
+    return 1 if mss == 0 or payload_len == 0 else -(-payload_len // mss)
+
+
+def segment_layout(sends: np.ndarray, flags: int = 0, align: int = 4):
+    """(n_frames, frames_bytes) a batch of sends (SEND_DTYPE) needs (fs_segment_layout, host-only
+    arithmetic: no device is touched). Raises FramesumError for an invalid send, flags or align."""
+    sends = np.ascontiguousarray(sends, dtype=SEND_DTYPE)
+    lib = load_library()
+    n, nbytes = ctypes.c_uint64(), ctypes.c_uint64()
+    st = lib.fs_segment_layout(sends.ctypes.data_as(ctypes.c_void_p), int(sends.size), flags, align, ctypes.byref(n),
+                               ctypes.byref(nbytes))
+    if st != FS_SUCCESS:
+        raise FramesumError(f"fs_segment_layout failed ({st}): {lib.fs_last_error(None).decode()}")
+    return int(n.value), int(nbytes.value)
+
 
 def shard_count(n: int, nshards: int, shard: int) -> int:
     """Frames of shard `shard` when n global frames go round-robin over nshards shards (C ABI)."""
