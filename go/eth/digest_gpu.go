@@ -297,6 +297,63 @@ func (g *GPU) SegmentBatch(sends []Send, appendFCS bool) ([][][]byte, error) {
 	return out, nil
 }
 
+// Run is one run of CoalesceBatch: the frames FirstFrame .. FirstFrame+NFrames-1 of the batch, all
+// accepted, whose payloads lie back to back in Payload. A TCP run's Flags are its first frame's
+// flags byte with the last frame's FIN and PSH; a UDP run's are 0.
+type Run struct {
+	FirstFrame uint32
+	NFrames    uint32
+	Flags      uint8
+	Payload    []byte
+}
+
+// CoalesceBatch is the RX delivery for many frames at once: what RecvEth's payload slices
+// (stacks/portstack.go:217, :239, :301-303) and TCPConn.recv's in-order append to the socket's
+// ring (stacks/tcpconn.go:347-369) do one frame at a time. The batch is verified as DigestBatch
+// does (wireFCS: the frames still carry their 4-byte FCS), the payload of every accepted frame
+// is gathered into one buffer, and consecutive TCP segments of one flow that continue each
+// other are reported as one run, so that a stack delivers one run per recv. verdicts (nil or
+// len(frames)) receives the per-frame RecvEth verdicts. The runs' payloads are slices of one
+// buffer.
+func (g *GPU) CoalesceBatch(frames [][]byte, mtu uint16, wireFCS bool, verdicts []Verdict) ([]Run, error) {
+	n := len(frames)
+	if verdicts != nil && len(verdicts) < n {
+		return nil, errors.New("framesum: verdicts too short")
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	var flags C.uint32_t
+	if wireFCS {
+		flags = C.FS_RX_FCS
+	}
+	buf, err := g.stage(frames, 0)
+	if err != nil {
+		return nil, err
+	}
+	payload := make([]byte, len(buf)+1)
+	cr := make([]C.fs_rx_run, n)
+	var totals C.fs_rx_totals
+	var vp *C.uint8_t
+	if verdicts != nil {
+		vp = (*C.uint8_t)(unsafe.Pointer(&verdicts[0]))
+	}
+	st := C.fs_coalesce_batch_host(g.ctx, (*C.uint8_t)(unsafe.Pointer(&buf[0])), C.uint64_t(len(buf)),
+		(*C.uint64_t)(unsafe.Pointer(&g.offs[0])), (*C.uint32_t)(unsafe.Pointer(&g.lens[0])),
+		C.uint32_t(n), C.uint32_t(mtu), flags, (*C.uint8_t)(unsafe.Pointer(&payload[0])), C.uint64_t(len(buf)),
+		&cr[0], nil, &totals, nil, vp)
+	if st != C.FS_SUCCESS {
+		return nil, g.lastErr()
+	}
+	runs := make([]Run, int(totals.n_runs))
+	for i := range runs {
+		off, ln := uint64(cr[i].payload_off), uint64(cr[i].payload_len)
+		runs[i] = Run{FirstFrame: uint32(cr[i].first_frame), NFrames: uint32(cr[i].n_frames),
+			Flags: uint8(cr[i].tcp_flags), Payload: payload[off : off+ln]}
+	}
+	return runs, nil
+}
+
 // GPUs is one host process's set of contexts, one per GPU, for NIC rings larger than one
 // PCIe link carries (fs_digest_batch_multi; BASELINE configs[4]).
 type GPUs struct {

@@ -211,6 +211,83 @@ fs_status fs_segment_batch_host(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n
                                 uint8_t* frames, uint64_t frames_bytes, uint64_t* offsets, uint32_t* lengths,
                                 fs_digest* out, uint8_t* status);
 
+/* RX coalesce, device-resident: verify a batch and gather the payload of every accepted frame into one
+ * contiguous buffer, reporting the runs of consecutive TCP segments that continue each other (what a
+ * NIC calls LRO/GRO), so that a stack delivers one run per recv instead of one frame. The mirror of
+ * fs_segment_batch: segmenting sends and coalescing the frames gives the sends' payload back. The
+ * reference does this one frame at a time after RecvEth: stacks/portstack.go:217, :239 and :301-303
+ * slice the payload out of the frame, and TCPConn.recv (stacks/tcpconn.go:347-369) checks that the
+ * segment is the next in order and appends it to the socket's ring (`sock.rx.Write(payload)`, :369).
+ *
+ * out / status are bit for bit what fs_digest_batch(..., mtu, ...) reports for the batch, with
+ * FS_RX_FCS what fs_digest_batch_fcs reports (lengths then include the 4-byte FCS): the call runs
+ * that launch itself, automatic kernel choice and all. Either may be NULL and then goes to scratch
+ * of the context.
+ *
+ * A frame is accepted iff its verdict is FS_OK. Its payload is what RecvEth hands to the port: UDP
+ * frame[14 + IHL*4 + 8 : 14 + TotalLength), TCP frame[14 + IHL*4 + dataoff*4 : 14 + TotalLength).
+ * It is IP-bounded (trailing Ethernet padding and the FCS are not part of it) and may be empty (a
+ * pure ACK).
+ *
+ * `payload` receives the payloads of the accepted frames in batch order, back to back: a frame's
+ * bytes start at the sum of the payload lengths of the accepted frames before it, and
+ * totals->payload_bytes is the sum over all of them. A frame whose payload would end beyond
+ * payload_cap is not copied: none of its bytes is written and nothing else about the result
+ * changes, so the caller compares payload_bytes with payload_cap. Bytes of `payload` that belong to
+ * no copied frame are not written (not even read and written back).
+ *
+ * Frame i joins frame i - 1 iff both are accepted, both are TCP with IHL 5 and data offset 5, both
+ * payloads are non-empty, neither has SYN, RST or URG set, frame i - 1 has neither FIN nor PSH set,
+ * Seq(i) == Seq(i - 1) + payload_len(i - 1) mod 2^32, and their 54-byte headers are equal in every
+ * byte except the fields fs_segment_batch varies per segment: IPv4 TotalLength, ID and checksum, TCP
+ * Seq, the FIN and PSH bits, and the TCP checksum (the fragment fields are compared as bytes, not
+ * interpreted, as RecvEth does not interpret them). A run is a maximal chain of joined frames; an
+ * accepted frame that joins nothing is a run of one (UDP, TCP with options, pure ACKs). Runs are
+ * listed in order of first_frame: runs[0 .. totals->n_runs) are written, the entries beyond are not.
+ * run_of[i] (nullable) is frame i's run index, or 0xFFFFFFFF for a frame that was not accepted.
+ *
+ * FS_E_INVALID, checked on the host before any device work: a null ctx, frames, offsets, lengths,
+ * runs or totals; a null payload with payload_cap not 0; flags other than 0 or FS_RX_FCS; n above
+ * 2^31; frames not 4-byte aligned (as fs_digest_batch). n of 0 is success: it writes zero totals and
+ * nothing else.
+ *
+ * All pointers are DEVICE pointers; `runs` has room for n entries. Asynchronous on `stream`. The
+ * call's scratch (24 bytes per frame, and out / status when they are NULL) belongs to the context
+ * and grows with n, so the coalesce calls of one context go on one stream or are ordered by the
+ * caller; a call with a larger n than any before waits for the device while it reallocates.
+ * fs_ctx_set_workgroups caps the grids of these kernels too (uncapped: up to 8 workgroups of 256
+ * lanes per compute unit); fs_ctx_set_kernel applies to the digest launch only. */
+#define FS_RX_FCS 1u /* frames carry their 4-byte FCS: verdicts as fs_digest_batch_fcs gives them */
+
+typedef struct fs_rx_run {  /* 24 bytes, no padding */
+    uint64_t payload_off;   /* the run's bytes are payload[payload_off : payload_off + payload_len) */
+    uint32_t payload_len;
+    uint32_t first_frame;   /* batch index of the run's first frame */
+    uint32_t n_frames;      /* frames first_frame .. first_frame + n_frames - 1, all accepted */
+    uint8_t tcp_flags;      /* TCP: first frame's flags byte | (last frame's FIN, PSH); UDP: 0 */
+    uint8_t reserved[3];    /* written as 0 */
+} fs_rx_run;
+
+typedef struct fs_rx_totals {
+    uint64_t payload_bytes;
+    uint32_t n_runs;
+    uint32_t reserved;
+} fs_rx_totals;
+
+fs_status fs_coalesce_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                            uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
+                            fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals, fs_digest* out, uint8_t* status,
+                            void* stream);
+
+/* fs_coalesce_batch with every pointer in HOST memory: copies the batch's byte span (inside
+ * frames_bytes, which bounds every frame) to the device, coalesces, copies the written part of the
+ * payload, runs[0 .. n_runs), run_of, the totals, out and status back (on the context's compute
+ * stream), and returns when they are written. `frames` needs no alignment here. */
+fs_status fs_coalesce_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                                 const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload,
+                                 uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals,
+                                 fs_digest* out, uint8_t* status);
+
 /* RX of raw wire frames that still carry their 4-byte FCS (NICs that do not strip it;
  * SURVEY.md §8f rank 4, not in the reference): lengths[i] includes the FCS. out/status are
  * fs_digest_batch's for frame[0:len-4), the bytes RecvEth would receive, except that status

@@ -10,7 +10,11 @@ from .framesum import (  # noqa: F401
     FCS_APPEND,
     FILL_CSUM,
     FS_ERR_FCS,
+    NO_RUN,
+    RUN_DTYPE,
+    RX_FCS,
     SEND_DTYPE,
+    TOTALS_DTYPE,
     VERDICTS,
     Digest,
     Engine,
@@ -24,6 +28,7 @@ from .framesum import (  # noqa: F401
     shard_count,
     shard_slab_bytes,
     split_digests,
+    split_runs,
 )
 
 __all__ = [
@@ -32,7 +37,11 @@ __all__ = [
     "FCS_APPEND",
     "FILL_CSUM",
     "FS_ERR_FCS",
+    "NO_RUN",
+    "RUN_DTYPE",
+    "RX_FCS",
     "SEND_DTYPE",
+    "TOTALS_DTYPE",
     "VERDICTS",
     "Digest",
     "Engine",
@@ -46,4 +55,5 @@ __all__ = [
     "shard_count",
     "shard_slab_bytes",
     "split_digests",
+    "split_runs",
 ]

@@ -99,6 +99,13 @@ struct fs_ctx {
     uint8_t* seg_d_frames = nullptr;
     uint8_t* seg_d_arrays = nullptr;
     uint64_t seg_cap_payload = 0, seg_cap_frames = 0, seg_cap_arrays = 0;
+    // RX coalesce: the kernels' scratch, out / status when the caller passes none, and the device
+    // buffers of fs_coalesce_batch_host (payload; runs, run_of and totals)
+    uint8_t* co_scratch = nullptr;
+    uint8_t* co_results = nullptr;
+    uint8_t* co_d_payload = nullptr;
+    uint8_t* co_d_arrays = nullptr;
+    uint64_t co_cap_scratch = 0, co_cap_results = 0, co_cap_payload = 0, co_cap_arrays = 0;
     std::string err;
 };
 
@@ -410,6 +417,10 @@ fs_status fs_ctx_destroy(fs_ctx* ctx) {
     (void)hipFree(ctx->seg_d_payload);
     (void)hipFree(ctx->seg_d_frames);
     (void)hipFree(ctx->seg_d_arrays);
+    (void)hipFree(ctx->co_scratch);
+    (void)hipFree(ctx->co_results);
+    (void)hipFree(ctx->co_d_payload);
+    (void)hipFree(ctx->co_d_arrays);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->h_report) (void)hipHostFree(const_cast<uint32_t*>(ctx->h_report));
     (void)hipFree(ctx->d_tables);
@@ -888,7 +899,7 @@ static fs_status segment_grow(fs_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t 
     (void)hipFree(*p);
     *p = nullptr;
     *cap = 0;
-    if (hipMalloc(p, bytes + 256) != hipSuccess) return set_err(ctx, FS_E_NOMEM, "fs_segment_batch_host: hipMalloc staging");
+    if (hipMalloc(p, bytes + 256) != hipSuccess) return set_err(ctx, FS_E_NOMEM, "hipMalloc of a staging buffer");
     *cap = bytes + 256;
     return FS_SUCCESS;
 }
@@ -948,6 +959,137 @@ fs_status fs_segment_batch_host(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n
     if (status) FS_HIP_DRAIN(ctx, hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ks));
     FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
     ctx->host_dirty = false;
+    return FS_SUCCESS;
+}
+
+// ---- RX coalesce (fs_coalesce_batch / fs_coalesce_batch_host) ----
+
+// Every check of a coalesce call, none of which needs a device. An empty batch needs only `totals`.
+static fs_status coalesce_check(fs_ctx* ctx, const char* fn, const void* frames, const void* offsets, const void* lengths,
+                                uint32_t n, uint32_t flags, const void* payload, uint64_t payload_cap, const void* runs,
+                                const void* totals, bool aligned) {
+    if (flags & ~(uint32_t)FS_RX_FCS) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": flags must be 0 or FS_RX_FCS");
+    if (n > kMaxFrames) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": n too large (at most 2^31 frames per call)");
+    if (!totals) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");
+    if (n == 0) return FS_SUCCESS;
+    if (!frames || !offsets || !lengths || !runs) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");
+    if (!payload && payload_cap != 0) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null payload with a non-zero payload_cap");
+    if (aligned && (reinterpret_cast<uintptr_t>(frames) & 3u))
+        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": frames must be 4-byte aligned");
+    return FS_SUCCESS;
+}
+
+// The digest launch and the coalesce launches of a checked, non-empty device-resident batch on `stream`.
+static fs_status coalesce_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                                  uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
+                                  fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals, fs_digest* out, uint8_t* status,
+                                  hipStream_t stream) {
+    fs_status st = segment_grow(ctx, &ctx->co_scratch, &ctx->co_cap_scratch, framesum::coalesce_scratch(n).bytes);
+    if (st == FS_SUCCESS && (!out || !status)) st = segment_grow(ctx, &ctx->co_results, &ctx->co_cap_results, (uint64_t)n * 9);
+    if (st != FS_SUCCESS) return st;
+    if (!out) out = reinterpret_cast<fs_digest*>(ctx->co_results);
+    if (!status) status = ctx->co_results + (uint64_t)n * 8;
+    FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, stream,
+                       (flags & FS_RX_FCS) ? framesum::FsOp::kFcs : framesum::FsOp::kDigest, nullptr, 0));
+    // up to 8 workgroups of 256 lanes per CU unless fs_ctx_set_workgroups caps the grids
+    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
+    FS_HIP(ctx, framesum::launch_coalesce(frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, run_of,
+                                          totals, ctx->co_scratch, wgs, stream));
+    return FS_SUCCESS;
+}
+
+fs_status fs_coalesce_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                            uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
+                            fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals, fs_digest* out, uint8_t* status,
+                            void* stream) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    const fs_status st = coalesce_check(ctx, "fs_coalesce_batch", frames, offsets, lengths, n, flags, payload, payload_cap,
+                                        runs, totals, true);
+    if (st != FS_SUCCESS) return st;
+    FS_HIP(ctx, hipSetDevice(ctx->device));
+    if (n == 0) {
+        FS_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(fs_rx_totals), reinterpret_cast<hipStream_t>(stream)));
+        return FS_SUCCESS;
+    }
+    return coalesce_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, payload, payload_cap, runs, run_of, totals, out,
+                            status, reinterpret_cast<hipStream_t>(stream));
+}
+
+fs_status fs_coalesce_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                                 const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload,
+                                 uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals,
+                                 fs_digest* out, uint8_t* status) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    const fs_status ast = coalesce_check(ctx, "fs_coalesce_batch_host", frames, offsets, lengths, n, flags, payload,
+                                         payload_cap, runs, totals, false);
+    if (ast != FS_SUCCESS) return ast;
+    if (n == 0) {
+        std::memset(totals, 0, sizeof(fs_rx_totals));
+        return FS_SUCCESS;
+    }
+    const uint32_t bad = framesum::plan::first_frame_out_of_range(offsets, lengths, n, frames_bytes);
+    if (bad < n)
+        return set_err(ctx, FS_E_INVALID, "fs_coalesce_batch_host: frame " + std::to_string(bad) + " ends past frames_bytes");
+    // the staged span [lo, hi), and the most payload the batch can hold
+    uint64_t lo = UINT64_MAX, hi = 0, most = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t o = offsets[i], e = o + lengths[i];
+        lo = o < lo ? o : lo;
+        hi = e > hi ? e : hi;
+        most += lengths[i];
+    }
+    const uint64_t d_cap = payload_cap < most ? payload_cap : most;
+    FS_HIP(ctx, hipSetDevice(ctx->device));
+    fs_status st = quiesce_host_streams(ctx);
+    if (st != FS_SUCCESS) return st;
+    uint64_t cpy_lo, cpy_hi;
+    framesum::plan::copy_span(lo, hi, frames_bytes, cpy_lo, cpy_hi);
+    HostSlot& sl = ctx->slot[0];
+    st = ensure_slot(ctx, sl, cpy_hi - cpy_lo + 64, n);
+    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->co_d_payload, &ctx->co_cap_payload, d_cap);
+    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->co_d_arrays, &ctx->co_cap_arrays, (uint64_t)n * 28 + 16);
+    if (st != FS_SUCCESS) return st;
+    ctx->host_dirty = true;  // until this call has waited for all of its work
+    const hipStream_t ks = ctx->compute_stream;
+    fs_rx_totals* d_totals = reinterpret_cast<fs_rx_totals*>(ctx->co_d_arrays);
+    fs_rx_run* d_runs = reinterpret_cast<fs_rx_run*>(ctx->co_d_arrays + 16);
+    uint32_t* d_run_of = reinterpret_cast<uint32_t*>(ctx->co_d_arrays + 16 + (uint64_t)n * 24);
+    if (sl.used) FS_HIP_DRAIN(ctx, hipStreamWaitEvent(ks, sl.consumed, 0));
+    // pinned memory (fs_host_alloc) is copied from and to directly; pageable memory goes through the
+    // runtime's own pinned staging
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_frames, frames + cpy_lo, cpy_hi - cpy_lo, hipMemcpyHostToDevice, ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_offsets, offsets, (size_t)n * 8, hipMemcpyHostToDevice, ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_lengths, lengths, (size_t)n * 4, hipMemcpyHostToDevice, ks));
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(sl.d_frames) - cpy_lo);
+    st = coalesce_enqueue(ctx, base, sl.d_offsets, sl.d_lengths, n, mtu, flags, ctx->co_d_payload, d_cap, d_runs,
+                          run_of ? d_run_of : nullptr, d_totals, sl.d_out, sl.d_status, ks);
+    if (st != FS_SUCCESS) {
+        drain_host_streams(ctx);
+        return st;
+    }
+    // the totals and how far the payload got written decide what else comes back
+    fs_rx_totals t;
+    uint64_t copied = 0;
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&t, d_totals, sizeof t, hipMemcpyDeviceToHost, ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&copied, ctx->co_scratch + framesum::coalesce_scratch(n).copied, 8,
+                                     hipMemcpyDeviceToHost, ks));
+    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
+    if (copied > d_cap || t.n_runs > n) {
+        drain_host_streams(ctx);
+        return set_err(ctx, FS_E_HIP, "fs_coalesce_batch_host: inconsistent totals from the device");
+    }
+    if (copied) FS_HIP_DRAIN(ctx, hipMemcpyAsync(payload, ctx->co_d_payload, copied, hipMemcpyDeviceToHost, ks));
+    if (t.n_runs) FS_HIP_DRAIN(ctx, hipMemcpyAsync(runs, d_runs, (size_t)t.n_runs * sizeof(fs_rx_run), hipMemcpyDeviceToHost, ks));
+    if (run_of) FS_HIP_DRAIN(ctx, hipMemcpyAsync(run_of, d_run_of, (size_t)n * 4, hipMemcpyDeviceToHost, ks));
+    if (out) FS_HIP_DRAIN(ctx, hipMemcpyAsync(out, sl.d_out, (size_t)n * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
+    if (status) FS_HIP_DRAIN(ctx, hipMemcpyAsync(status, sl.d_status, n, hipMemcpyDeviceToHost, ks));
+    FS_HIP_DRAIN(ctx, hipEventRecord(sl.consumed, ks));
+    sl.used = true;
+    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
+    ctx->host_dirty = false;
+    *totals = t;
     return FS_SUCCESS;
 }
 

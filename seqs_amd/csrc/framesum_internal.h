@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
+#include "../../include/framesum.h"
 #include "framesum_choice.h"
 
 namespace framesum {
@@ -83,5 +84,20 @@ hipError_t launch_segment(const uint8_t* d_block, const segment::Block& b, uint3
                           const uint8_t* payload, uint8_t* frames, uint64_t* offsets, uint32_t* lengths, void* out,
                           uint8_t* status, uint32_t mtu, uint32_t flags, uint32_t align, const SegTables* tables,
                           int workgroups, hipStream_t stream);
+
+// ---- RX coalesce (framesum_coalesce.hip). The launches that follow a batch's digest launch on
+// `stream`: classify, the scan's three steps and the copy (fs_coalesce_batch in include/framesum.h).
+// `status`: the batch's verdicts, as that digest launch writes them. `scratch`: coalesce_scratch(n).bytes
+// of device memory, 8-byte aligned, whose sub-arrays lie at the offsets CoScratch names; `copied` is
+// the 64-bit count of leading payload bytes the copy writes (the whole of it unless payload_cap cuts
+// it short). `max_workgroups` caps every grid.
+struct CoScratch {
+    uint64_t rec, payoff, partial, prefix, copied, runidx, hidx, bytes;
+};
+CoScratch coalesce_scratch(uint32_t n);
+hipError_t launch_coalesce(const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
+                           uint32_t flags, const uint8_t* status, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
+                           uint32_t* run_of, fs_rx_totals* totals, uint8_t* scratch, int max_workgroups,
+                           hipStream_t stream);
 
 }  // namespace framesum

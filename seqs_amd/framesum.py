@@ -52,6 +52,9 @@ VERDICTS = {
 FILL_CSUM = 1
 FCS_APPEND = 2
 FS_ERR_FCS = 14
+# fs_coalesce_batch flag: the frames carry their 4-byte FCS
+RX_FCS = 1
+NO_RUN = 0xFFFFFFFF  # run_of of a frame that was not accepted
 
 # Every symbol include/framesum.h declares (checked by tests/test_abi.py).
 EXPORTED_SYMBOLS = (
@@ -68,6 +71,8 @@ EXPORTED_SYMBOLS = (
     "fs_segment_layout",
     "fs_segment_batch",
     "fs_segment_batch_host",
+    "fs_coalesce_batch",
+    "fs_coalesce_batch_host",
     "fs_digest_batch_multi",
     "fs_ctx_set_kernel",
     "fs_ctx_set_workgroups",
@@ -88,6 +93,10 @@ DIGEST_DTYPE = np.dtype([("crc32", "<u4"), ("ip_csum", "<u2"), ("l4_csum", "<u2"
 SEND_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("payload_off", "<u8"), ("payload_len", "<u4"),
                        ("reserved", "<u4")])
 SEGMENT_MAX_FRAMES = 4096
+# fs_rx_run: one run of the RX coalesce (24 bytes, no padding), and fs_rx_totals (16 bytes)
+RUN_DTYPE = np.dtype([("payload_off", "<u8"), ("payload_len", "<u4"), ("first_frame", "<u4"), ("n_frames", "<u4"),
+                      ("tcp_flags", "u1"), ("reserved", "u1", (3,))])
+TOTALS_DTYPE = np.dtype([("payload_bytes", "<u8"), ("n_runs", "<u4"), ("reserved", "<u4")])
 
 
 class FramesumError(RuntimeError):
@@ -148,6 +157,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.fs_segment_batch.argtypes = [vp, vp, u32, vp, u64, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp]
     lib.fs_segment_batch_host.restype = i32
     lib.fs_segment_batch_host.argtypes = [vp, vp, u32, vp, u64, u32, u32, u32, vp, u64, vp, vp, vp, vp]
+    lib.fs_coalesce_batch.restype = i32
+    lib.fs_coalesce_batch.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp]
+    lib.fs_coalesce_batch_host.restype = i32
+    lib.fs_coalesce_batch_host.argtypes = [vp, vp, u64, vp, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp]
     if hasattr(lib, "fs_ctx_set_workgroups"):  # (absent from builds before round 4: same-box A/B runs)
         lib.fs_ctx_set_workgroups.restype = i32
         lib.fs_ctx_set_workgroups.argtypes = [vp, ctypes.c_int]
@@ -475,6 +488,73 @@ class Engine:
             f += cnt
         return res
 
+    # ---- RX coalesce ---------------------------------------------------------
+    def coalesce_device(self, frames, offsets, lengths, mtu: int = 0, flags: int = 0, payload=None, stream=None):
+        """Verify a device-resident batch and gather the payload of every accepted frame
+        (fs_coalesce_batch): `payload` (a uint8 CUDA tensor, else a new one of the frame buffer's
+        size) receives the payloads back to back; frames that would end past it are not copied.
+        Returns (payload, runs, run_of, totals, out, status) device tensors: runs (n, 24) uint8 =
+        RUN_DTYPE records of which the first totals' n_runs are written, run_of (n,) int32 (-1 =
+        NO_RUN), totals (16,) uint8 = one TOTALS_DTYPE record; out and status as digest_device gives
+        them (flags RX_FCS: as digest_fcs_device). Asynchronous on `stream`; split_runs() brings the
+        runs and totals to the host."""
+        import torch
+
+        n, out, status, stream = self._device_args(frames, offsets, lengths, None, None, stream)
+        dev = frames.device
+        if payload is None:
+            payload = torch.empty((frames.numel(),), dtype=torch.uint8, device=dev)
+        assert payload.is_cuda and payload.dtype == torch.uint8 and payload.is_contiguous()
+        runs = torch.empty((n, RUN_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        run_of = torch.empty((n,), dtype=torch.int32, device=dev)
+        totals = torch.empty((TOTALS_DTYPE.itemsize,), dtype=torch.uint8, device=dev)
+        vp = ctypes.c_void_p
+        st = self.lib.fs_coalesce_batch(
+            self._ctx, vp(frames.data_ptr()), vp(offsets.data_ptr()), vp(lengths.data_ptr()), n, mtu, flags,
+            vp(payload.data_ptr()), int(payload.numel()), vp(runs.data_ptr()), vp(run_of.data_ptr()),
+            vp(totals.data_ptr()), vp(out.data_ptr()), vp(status.data_ptr()), vp(stream.cuda_stream))
+        self._check(st, "fs_coalesce_batch")
+        return payload, runs, run_of, totals, out, status
+
+    def coalesce_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, mtu: int = 0, flags: int = 0,
+                      payload: Optional[np.ndarray] = None):
+        """coalesce_device from and to host memory (fs_coalesce_batch_host). `payload`: a writable
+        uint8 array to gather into, else a new zeroed one as long as the frames together. Returns
+        (payload, runs RUN_DTYPE[n_runs], run_of uint32, totals TOTALS_DTYPE scalar record, digests,
+        status) numpy arrays."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        n = int(lengths.size)
+        assert offsets.size == n, "offsets and lengths must describe the same frames"
+        if payload is None:
+            payload = np.zeros(int(lengths.sum(dtype=np.uint64)), dtype=np.uint8)
+        assert payload.dtype == np.uint8 and payload.flags["C_CONTIGUOUS"] and payload.flags["WRITEABLE"]
+        runs = np.zeros(n, dtype=RUN_DTYPE)
+        run_of = np.zeros(n, dtype=np.uint32)
+        totals = np.zeros(1, dtype=TOTALS_DTYPE)
+        out = np.zeros(n, dtype=DIGEST_DTYPE)
+        status = np.zeros(n, dtype=np.uint8)
+        vp = ctypes.c_void_p
+        st = self.lib.fs_coalesce_batch_host(
+            self._ctx, frames.ctypes.data_as(vp), frames.nbytes, offsets.ctypes.data_as(vp), lengths.ctypes.data_as(vp), n,
+            mtu, flags, payload.ctypes.data_as(vp), payload.nbytes, runs.ctypes.data_as(vp), run_of.ctypes.data_as(vp),
+            totals.ctypes.data_as(vp), out.ctypes.data_as(vp), status.ctypes.data_as(vp))
+        self._check(st, "fs_coalesce_batch_host")
+        return payload, runs[: int(totals["n_runs"][0])], run_of, totals[0], out, status
+
+    def coalesce_batch(self, frames: Sequence[bytes], mtu: int = 0) -> list:
+        """The reference's RX delivery for many frames (the payload slices of stacks/portstack.go:217,
+        :239, :301-303 and the in-order append of TCPConn.recv, stacks/tcpconn.go:347-369): one
+        (first_frame, n_frames, tcp_flags, payload_bytes) per run of the accepted frames, TCP segments
+        that continue each other delivered as one run."""
+        if len(frames) == 0:
+            return []
+        buf, offsets, lengths = pack_frames(frames, 1)
+        payload, runs, _, _, _, _ = self.coalesce_host(buf, offsets, lengths, mtu)
+        return [(int(r["first_frame"]), int(r["n_frames"]), int(r["tcp_flags"]),
+                 bytes(payload[int(r["payload_off"]) : int(r["payload_off"]) + int(r["payload_len"])])) for r in runs]
+
     # ---- host-staged path (numpy in, numpy out) -----------------------------
     def host_empty(self, shape, dtype=np.uint8) -> np.ndarray:
         """A numpy array in pinned host memory (fs_host_alloc), freed with the array."""
@@ -618,6 +698,15 @@ def segment_layout(sends: np.ndarray, flags: int = 0, align: int = 4):
     if st != FS_SUCCESS:
         raise FramesumError(f"fs_segment_layout failed ({st}): {lib.fs_last_error(None).decode()}")
     return int(n.value), int(nbytes.value)
+
+
+def split_runs(runs, totals):
+    """The host view of coalesce_device's `runs` and `totals` tensors (this waits for them):
+    (RUN_DTYPE[n_runs], payload_bytes, n_runs)."""
+    t = np.ascontiguousarray(totals.cpu().numpy()).view(TOTALS_DTYPE)[0]
+    k = int(t["n_runs"])
+    r = np.ascontiguousarray(runs[:k].cpu().numpy()).reshape(-1).view(RUN_DTYPE)
+    return r, int(t["payload_bytes"]), k
 
 
 def shard_count(n: int, nshards: int, shard: int) -> int:
