@@ -118,18 +118,23 @@ def flow_header(rng, sport: int = 0x1234, flags: int = ACK) -> bytes:
     return bytes(h)
 
 
-def tcp_frame(hdr: bytes, seq: int, payload: bytes, flags=None, ident=None, options: bytes = b"", pad: int = 0) -> bytes:
+def tcp_frame(hdr: bytes, seq: int, payload: bytes, flags=None, ident=None, options: bytes = b"", pad: int = 0,
+              ip_options: bytes = b"") -> bytes:
     """One TCP segment of the flow `hdr`: Seq, TotalLength, (flags, ID), `options` (a multiple of 4
-    bytes) and `pad` bytes of Ethernet padding behind the IP datagram."""
+    bytes) and `pad` bytes of Ethernet padding behind the IP datagram. `ip_options` (a multiple of 4
+    bytes): IPv4 options; IHL and TotalLength count them and the TCP header lies behind them."""
+    assert len(options) % 4 == 0 and len(ip_options) % 4 == 0 and len(ip_options) <= 40
     h = bytearray(hdr)
-    h[16:18] = (40 + len(options) + len(payload)).to_bytes(2, "big")
+    h[16:18] = (40 + len(ip_options) + len(options) + len(payload)).to_bytes(2, "big")
     h[38:42] = (seq % (1 << 32)).to_bytes(4, "big")
     h[46] = (5 + len(options) // 4) << 4
     if flags is not None:
         h[47] = flags
     if ident is not None:
         h[18:20] = ident.to_bytes(2, "big")
-    return bytes(h) + options + bytes(payload) + bytes(pad)
+    if ip_options:
+        h[14] = (h[14] & 0xF0) | (5 + len(ip_options) // 4)
+    return bytes(h[:34]) + bytes(ip_options) + bytes(h[34:]) + options + bytes(payload) + bytes(pad)
 
 
 def udp_frame(rng, payload: bytes, pad: int = 0) -> bytes:
@@ -180,6 +185,45 @@ def pack(frames, lead: int = 0, seed: int = 0, tail: int = 64):
     buf = np.random.default_rng(1000 + seed).integers(0, 256, lead + total + tail, dtype=np.uint8)
     buf[lead : lead + total] = packed[:total]
     return buf, offs + np.uint64(lead), lens
+
+
+def pack_at(frames, order, gaps, seed: int = 0, tail: int = 64):
+    """The frames laid out in memory in `order` (order[k]: the batch index of the k-th frame in
+    memory, every index once) with gaps[k] bytes of noise in front of the k-th, and `tail` bytes of it
+    behind the last: (buf, offsets, lengths), offsets and lengths in BATCH order. The buffer itself
+    starts 4-byte aligned, as pack()'s does."""
+    order = [int(i) for i in order]
+    assert sorted(order) == list(range(len(frames))) and len(gaps) == len(frames)
+    total = sum(len(f) for f in frames) + sum(int(g) for g in gaps)
+    buf = np.random.default_rng(2000 + seed).integers(0, 256, total + tail, dtype=np.uint8)
+    offs = np.zeros(len(frames), dtype=np.uint64)
+    lens = np.array([len(f) for f in frames], dtype=np.uint32)
+    at = 0
+    for i, g in zip(order, gaps):
+        at += int(g)
+        offs[i] = at
+        buf[at : at + len(frames[i])] = np.frombuffer(bytes(frames[i]), dtype=np.uint8)
+        at += len(frames[i])
+    return buf, offs, lens
+
+
+def with_fcs(frames, damage=()) -> list:
+    """Every frame with its FCS behind it, written by the C oracle; the frames' own bytes (checksum
+    fields included) stay as they are. One bit of the FCS of the frames listed in `damage` is flipped."""
+    from oracle import coracle
+
+    lens = np.array([len(f) for f in frames], dtype=np.uint32)
+    offs = np.zeros(len(frames), dtype=np.uint64)
+    offs[1:] = np.cumsum(lens[:-1].astype(np.uint64) + np.uint64(4))
+    buf = np.zeros(int(lens.sum()) + 4 * len(frames) + 8, dtype=np.uint8)
+    for f, o in zip(frames, offs):
+        buf[int(o) : int(o) + len(f)] = np.frombuffer(bytes(f), dtype=np.uint8)
+    coracle.fill_batch(buf, offs, lens, 0, coracle.FCS_APPEND)
+    for k, i in enumerate(damage):
+        buf[int(offs[i]) + int(lens[i]) + k % 4] ^= np.uint8(1 << (k % 8))
+    out = [buf[int(o) : int(o) + int(n) + 4].tobytes() for o, n in zip(offs, lens)]
+    assert all(o[: len(f)] == bytes(f) for o, f in zip(out, frames))
+    return out
 
 
 def kat_frames() -> list:
