@@ -354,6 +354,81 @@ func (g *GPU) CoalesceBatch(frames [][]byte, mtu uint16, wireFCS bool, verdicts 
 	return runs, nil
 }
 
+// Flow is one flow of CoalesceFlowsBatch: the accepted frames of the batch that share protocol,
+// addresses and ports. Frames are their batch indices in batch order, Payload their payloads back to
+// back, and Runs the maximal chains of TCP segments that continue each other (a Run's FirstFrame
+// counts within Frames here); the runs' payloads are slices of Payload.
+type Flow struct {
+	Proto        uint8
+	Src, Dst     [4]byte
+	SPort, DPort uint16
+	Frames       []uint32
+	Payload      []byte
+	Runs         []Run
+}
+
+// CoalesceFlowsBatch is CoalesceBatch for a PortStack with more than one open connection, whose
+// segments interleave on the wire (A0 B0 A1 B1 ...): what findPort (stacks/portstack.go:309, :246
+// for UDP) and TCPConn.recv's remote-address and in-order checks (stacks/tcpconn.go:347-369) do one
+// frame at a time. The accepted frames are grouped by flow, flows in the order of their first frames,
+// each flow's payload is gathered contiguously and the runs are found inside each flow, so that a
+// frame of another connection between two segments does not end a run.
+func (g *GPU) CoalesceFlowsBatch(frames [][]byte, mtu uint16, wireFCS bool, verdicts []Verdict) ([]Flow, error) {
+	n := len(frames)
+	if verdicts != nil && len(verdicts) < n {
+		return nil, errors.New("framesum: verdicts too short")
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	var flags C.uint32_t
+	if wireFCS {
+		flags = C.FS_RX_FCS
+	}
+	buf, err := g.stage(frames, 0)
+	if err != nil {
+		return nil, err
+	}
+	payload := make([]byte, len(buf)+1)
+	cr := make([]C.fs_rx_run, n)
+	cf := make([]C.fs_rx_flow, n)
+	order := make([]uint32, n)
+	var ft C.fs_rx_flow_totals
+	var vp *C.uint8_t
+	if verdicts != nil {
+		vp = (*C.uint8_t)(unsafe.Pointer(&verdicts[0]))
+	}
+	st := C.fs_coalesce_flows_batch_host(g.ctx, (*C.uint8_t)(unsafe.Pointer(&buf[0])), C.uint64_t(len(buf)),
+		(*C.uint64_t)(unsafe.Pointer(&g.offs[0])), (*C.uint32_t)(unsafe.Pointer(&g.lens[0])),
+		C.uint32_t(n), C.uint32_t(mtu), flags, (*C.uint8_t)(unsafe.Pointer(&payload[0])), C.uint64_t(len(buf)),
+		&cr[0], &cf[0], (*C.uint32_t)(unsafe.Pointer(&order[0])), nil, &ft, nil, vp)
+	if st != C.FS_SUCCESS {
+		return nil, g.lastErr()
+	}
+	order = order[:int(ft.n_accepted)]
+	flows := make([]Flow, int(ft.n_flows))
+	for i := range flows {
+		off, ln := uint64(cf[i].payload_off), uint64(cf[i].payload_len)
+		f0, nf := int(cf[i].first_frame), int(cf[i].n_frames)
+		r0, nr := int(cf[i].first_run), int(cf[i].n_runs)
+		first := frames[order[f0]]
+		l4 := 14 + 4*int(first[14]&15)
+		fl := Flow{Proto: first[23], SPort: uint16(first[l4])<<8 | uint16(first[l4+1]),
+			DPort: uint16(first[l4+2])<<8 | uint16(first[l4+3]), Frames: order[f0 : f0+nf],
+			Payload: payload[off : off+ln], Runs: make([]Run, nr)}
+		copy(fl.Src[:], first[26:30])
+		copy(fl.Dst[:], first[30:34])
+		for k := range fl.Runs {
+			r := &cr[r0+k]
+			ro, rl := uint64(r.payload_off), uint64(r.payload_len)
+			fl.Runs[k] = Run{FirstFrame: uint32(r.first_frame) - uint32(f0), NFrames: uint32(r.n_frames),
+				Flags: uint8(r.tcp_flags), Payload: payload[ro : ro+rl]}
+		}
+		flows[i] = fl
+	}
+	return flows, nil
+}
+
 // GPUs is one host process's set of contexts, one per GPU, for NIC rings larger than one
 // PCIe link carries (fs_digest_batch_multi; BASELINE configs[4]).
 type GPUs struct {

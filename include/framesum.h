@@ -288,6 +288,86 @@ fs_status fs_coalesce_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fr
                                  uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals,
                                  fs_digest* out, uint8_t* status);
 
+/* Flow-aware RX coalesce, device-resident: fs_coalesce_batch for traffic in which the segments of
+ * several connections interleave (A0 B0 A1 B1 ...), where joining a segment only to the frame right
+ * before it finds runs of one. The accepted frames are grouped by flow, each flow's payload is
+ * gathered contiguously, and the runs are found inside each flow. The reference demultiplexes one
+ * frame at a time: findPort(ps.portsTCP, thdr.DestinationPort) (stacks/portstack.go:309, :246 for
+ * UDP) picks the socket, and TCPConn.recv checks the remote address and the in-order Seq before
+ * sock.rx.Write(payload) (stacks/tcpconn.go:347-369).
+ *
+ * Verdicts and payload ranges: out / status, accepted (= FS_OK), a frame's payload range, FS_RX_FCS
+ * and the payload_cap rule (a frame whose payload would end beyond payload_cap is not copied, and
+ * nothing else about the result changes) are exactly fs_coalesce_batch's; the call runs the same
+ * digest launch.
+ *
+ * The flow key of an accepted frame is 13 bytes: the protocol frame[23], the source and destination
+ * IPv4 address frame[26 : 34), and the source and destination port frame[L4 : L4 + 4) with L4 = 14 +
+ * 4 * IHL (with IP options the ports move). MAC addresses are not part of it. A flow is the set of
+ * accepted frames with equal keys.
+ *
+ * Flows are numbered by the batch index of their first frame, ascending. The delivery order is flow
+ * 0's frames in batch order, then flow 1's, and so on. order[k], for k < totals->n_accepted, is the
+ * batch index of the k-th frame in delivery order; the entries beyond are not written. `order` is
+ * required and has room for n entries; `flows` (room for n entries) may be NULL.
+ *
+ * `payload` receives the payloads back to back in delivery order, so a flow's bytes are contiguous.
+ *
+ * order[k] joins order[k - 1] under fs_coalesce_batch's join rule, unchanged. The header bytes it
+ * compares include the key bytes of the frames that can join, so frames of different flows never
+ * join. A frame that is not accepted belongs to no flow, and, unlike in fs_coalesce_batch, it does
+ * not break a run by standing between two frames in the batch; if it carried bytes of the flow, the
+ * Seq gap breaks the run.
+ *
+ * Runs are maximal chains, listed in delivery order: runs[0 .. totals->n_runs) are written. In a
+ * run of this call first_frame is an index into `order`: the run's frames are order[first_frame ..
+ * first_frame + n_frames). run_of[i] (nullable) is frame i's run index, or 0xFFFFFFFF for a frame
+ * that was not accepted. flows[f], f < totals->n_flows, describes flow f: its bytes in `payload`,
+ * its runs in `runs`, its frames in `order`.
+ *
+ * When every flow's frames are contiguous in the batch and no rejected frame stands between two
+ * frames that join, payload, runs and run_of are byte for byte fs_coalesce_batch's, and order is
+ * ascending. (A run's first_frame counts accepted frames here: it is the batch index when every
+ * frame before the run is accepted, and order[first_frame] is the batch index always.)
+ *
+ * FS_E_INVALID, checked on the host before any device work: what fs_coalesce_batch rejects, a null
+ * order, and n above 2^30 (the flow table's index stays 32-bit). n of 0 is success: it writes zero
+ * totals and nothing else.
+ *
+ * All pointers are DEVICE pointers. Asynchronous on `stream`. The call's scratch belongs to the
+ * context and grows with n, as fs_coalesce_batch's does (one stream, or ordered by the caller): 68
+ * bytes per frame, 8 bytes per slot of the flow table (the power of two from 2 n up: 16 to 32
+ * bytes per frame) and the sort's temporary storage (rocPRIM asks for 8 bytes per frame): 92 bytes
+ * per frame at 65,536 frames; a call with a larger n than any before waits for the device while it
+ * reallocates. fs_ctx_set_workgroups caps the grids of this call's own kernels; the sort's launches
+ * are the rocPRIM library's and size themselves. */
+typedef struct fs_rx_flow {      /* 32 bytes, no padding */
+    uint64_t payload_off;        /* the flow's bytes: payload[payload_off : payload_off + payload_len) */
+    uint64_t payload_len;
+    uint32_t first_run, n_runs;  /* runs[first_run .. first_run + n_runs) */
+    uint32_t first_frame, n_frames; /* order[first_frame .. first_frame + n_frames) */
+} fs_rx_flow;
+
+typedef struct fs_rx_flow_totals { /* 24 bytes */
+    uint64_t payload_bytes;
+    uint32_t n_runs, n_flows, n_accepted, reserved /* written 0 */;
+} fs_rx_flow_totals;
+
+fs_status fs_coalesce_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                                  uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
+                                  fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
+                                  fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream);
+
+/* fs_coalesce_flows_batch with every pointer in HOST memory, as fs_coalesce_batch_host: copies the
+ * batch's byte span to the device, coalesces, copies the written part of the payload, runs[0 ..
+ * n_runs), flows[0 .. n_flows), order[0 .. n_accepted), run_of, the totals, out and status back, and
+ * returns when they are written. `frames` needs no alignment here. */
+fs_status fs_coalesce_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes,
+                                       const uint64_t* offsets, const uint32_t* lengths, uint32_t n, uint32_t mtu,
+                                       uint32_t flags, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
+                                       fs_rx_flow* flows, uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals,
+                                       fs_digest* out, uint8_t* status);
+
 /* RX of raw wire frames that still carry their 4-byte FCS (NICs that do not strip it;
  * SURVEY.md §8f rank 4, not in the reference): lengths[i] includes the FCS. out/status are
  * fs_digest_batch's for frame[0:len-4), the bytes RecvEth would receive, except that status

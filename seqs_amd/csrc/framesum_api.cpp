@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/framesum.h"
+#include "framesum_flows.h"
 #include "framesum_internal.h"
 #include "framesum_plan.h"
 #include "framesum_segment.h"
@@ -106,6 +107,14 @@ struct fs_ctx {
     uint8_t* co_d_payload = nullptr;
     uint8_t* co_d_arrays = nullptr;
     uint64_t co_cap_scratch = 0, co_cap_results = 0, co_cap_payload = 0, co_cap_arrays = 0;
+    // flow-aware RX coalesce: the kernels' scratch and the device result arrays of
+    // fs_coalesce_flows_batch_host (out / status and the payload share the buffers above). The hash
+    // mask and the steps are all ones / all steps unless the test library's setters change them.
+    uint8_t* fl_scratch = nullptr;
+    uint8_t* fl_d_arrays = nullptr;
+    uint64_t fl_cap_scratch = 0, fl_cap_arrays = 0;
+    uint32_t flow_hash_mask = 0xFFFFFFFFu;
+    uint32_t flow_steps = framesum::kFlowStepsAll;
     std::string err;
 };
 
@@ -421,6 +430,8 @@ fs_status fs_ctx_destroy(fs_ctx* ctx) {
     (void)hipFree(ctx->co_results);
     (void)hipFree(ctx->co_d_payload);
     (void)hipFree(ctx->co_d_arrays);
+    (void)hipFree(ctx->fl_scratch);
+    (void)hipFree(ctx->fl_d_arrays);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->h_report) (void)hipHostFree(const_cast<uint32_t*>(ctx->h_report));
     (void)hipFree(ctx->d_tables);
@@ -1093,6 +1104,147 @@ fs_status fs_coalesce_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fr
     return FS_SUCCESS;
 }
 
+// ---- Flow-aware RX coalesce (fs_coalesce_flows_batch / fs_coalesce_flows_batch_host) ----
+
+static fs_status flows_check(fs_ctx* ctx, const char* fn, const void* frames, const void* offsets, const void* lengths,
+                             uint32_t n, uint32_t flags, const void* payload, uint64_t payload_cap, const void* runs,
+                             const void* order, const void* totals, bool aligned) {
+    if (n > framesum::flows::kMaxFrames)
+        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": n too large (at most 2^30 frames per call)");
+    const fs_status st =
+        coalesce_check(ctx, fn, frames, offsets, lengths, n, flags, payload, payload_cap, runs, totals, aligned);
+    if (st != FS_SUCCESS) return st;
+    if (n != 0 && !order) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");  // (as `runs`)
+    return FS_SUCCESS;
+}
+
+// The digest launch and the flow coalesce launches of a checked, non-empty device-resident batch on
+// `stream`. `copied_at` (nullable): where in the context's scratch the count of written payload bytes lies.
+static fs_status flows_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                               uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
+                               fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
+                               fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, hipStream_t stream,
+                               uint64_t* copied_at) {
+    const framesum::FlowScratch s = framesum::flows_scratch(n);
+    if (s.sort_bytes == 0) return set_err(ctx, FS_E_HIP, "fs_coalesce_flows_batch: the sort reports no temporary storage size");
+    fs_status st = segment_grow(ctx, &ctx->fl_scratch, &ctx->fl_cap_scratch, s.bytes);
+    if (st == FS_SUCCESS && (!out || !status)) st = segment_grow(ctx, &ctx->co_results, &ctx->co_cap_results, (uint64_t)n * 9);
+    if (st != FS_SUCCESS) return st;
+    if (!out) out = reinterpret_cast<fs_digest*>(ctx->co_results);
+    if (!status) status = ctx->co_results + (uint64_t)n * 8;
+    if (copied_at) *copied_at = s.copied;
+    if (ctx->flow_steps == framesum::kFlowStepsAll)
+        FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, stream,
+                           (flags & FS_RX_FCS) ? framesum::FsOp::kFcs : framesum::FsOp::kDigest, nullptr, 0));
+    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
+    FS_HIP(ctx, framesum::launch_coalesce_flows(frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, flows,
+                                                order, run_of, totals, ctx->fl_scratch, s, ctx->flow_hash_mask, wgs,
+                                                ctx->flow_steps, stream));
+    return FS_SUCCESS;
+}
+
+fs_status fs_coalesce_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                                  uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
+                                  fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
+                                  fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    const fs_status st = flows_check(ctx, "fs_coalesce_flows_batch", frames, offsets, lengths, n, flags, payload,
+                                     payload_cap, runs, order, totals, true);
+    if (st != FS_SUCCESS) return st;
+    FS_HIP(ctx, hipSetDevice(ctx->device));
+    if (n == 0) {
+        FS_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(fs_rx_flow_totals), reinterpret_cast<hipStream_t>(stream)));
+        return FS_SUCCESS;
+    }
+    return flows_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, payload, payload_cap, runs, flows, order, run_of,
+                         totals, out, status, reinterpret_cast<hipStream_t>(stream), nullptr);
+}
+
+fs_status fs_coalesce_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes,
+                                       const uint64_t* offsets, const uint32_t* lengths, uint32_t n, uint32_t mtu,
+                                       uint32_t flags, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
+                                       fs_rx_flow* flows, uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals,
+                                       fs_digest* out, uint8_t* status) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    const fs_status ast = flows_check(ctx, "fs_coalesce_flows_batch_host", frames, offsets, lengths, n, flags, payload,
+                                      payload_cap, runs, order, totals, false);
+    if (ast != FS_SUCCESS) return ast;
+    if (n == 0) {
+        std::memset(totals, 0, sizeof(fs_rx_flow_totals));
+        return FS_SUCCESS;
+    }
+    const uint32_t bad = framesum::plan::first_frame_out_of_range(offsets, lengths, n, frames_bytes);
+    if (bad < n)
+        return set_err(ctx, FS_E_INVALID,
+                       "fs_coalesce_flows_batch_host: frame " + std::to_string(bad) + " ends past frames_bytes");
+    // the staged span [lo, hi), and the most payload the batch can hold
+    uint64_t lo = UINT64_MAX, hi = 0, most = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t o = offsets[i], e = o + lengths[i];
+        lo = o < lo ? o : lo;
+        hi = e > hi ? e : hi;
+        most += lengths[i];
+    }
+    const uint64_t d_cap = payload_cap < most ? payload_cap : most;
+    FS_HIP(ctx, hipSetDevice(ctx->device));
+    fs_status st = quiesce_host_streams(ctx);
+    if (st != FS_SUCCESS) return st;
+    uint64_t cpy_lo, cpy_hi;
+    framesum::plan::copy_span(lo, hi, frames_bytes, cpy_lo, cpy_hi);
+    HostSlot& sl = ctx->slot[0];
+    st = ensure_slot(ctx, sl, cpy_hi - cpy_lo + 64, n);
+    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->co_d_payload, &ctx->co_cap_payload, d_cap);
+    // totals (24), then per frame: a run (24), a flow (32), order (4), run_of (4)
+    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->fl_d_arrays, &ctx->fl_cap_arrays, (uint64_t)n * 64 + 24);
+    if (st != FS_SUCCESS) return st;
+    ctx->host_dirty = true;  // until this call has waited for all of its work
+    const hipStream_t ks = ctx->compute_stream;
+    fs_rx_flow_totals* d_totals = reinterpret_cast<fs_rx_flow_totals*>(ctx->fl_d_arrays);
+    fs_rx_run* d_runs = reinterpret_cast<fs_rx_run*>(ctx->fl_d_arrays + 24);
+    fs_rx_flow* d_flows = reinterpret_cast<fs_rx_flow*>(ctx->fl_d_arrays + 24 + (uint64_t)n * 24);
+    uint32_t* d_order = reinterpret_cast<uint32_t*>(ctx->fl_d_arrays + 24 + (uint64_t)n * 56);
+    uint32_t* d_run_of = reinterpret_cast<uint32_t*>(ctx->fl_d_arrays + 24 + (uint64_t)n * 60);
+    if (sl.used) FS_HIP_DRAIN(ctx, hipStreamWaitEvent(ks, sl.consumed, 0));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_frames, frames + cpy_lo, cpy_hi - cpy_lo, hipMemcpyHostToDevice, ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_offsets, offsets, (size_t)n * 8, hipMemcpyHostToDevice, ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_lengths, lengths, (size_t)n * 4, hipMemcpyHostToDevice, ks));
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(sl.d_frames) - cpy_lo);
+    uint64_t copied_at = 0;
+    st = flows_enqueue(ctx, base, sl.d_offsets, sl.d_lengths, n, mtu, flags, ctx->co_d_payload, d_cap, d_runs,
+                       flows ? d_flows : nullptr, d_order, run_of ? d_run_of : nullptr, d_totals, sl.d_out, sl.d_status, ks,
+                       &copied_at);
+    if (st != FS_SUCCESS) {
+        drain_host_streams(ctx);
+        return st;
+    }
+    // the totals and how far the payload got written decide what else comes back
+    fs_rx_flow_totals t;
+    uint64_t copied = 0;
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&t, d_totals, sizeof t, hipMemcpyDeviceToHost, ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&copied, ctx->fl_scratch + copied_at, 8, hipMemcpyDeviceToHost, ks));
+    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
+    if (copied > d_cap || t.n_accepted > n || t.n_runs > t.n_accepted || t.n_flows > t.n_runs) {
+        drain_host_streams(ctx);
+        return set_err(ctx, FS_E_HIP, "fs_coalesce_flows_batch_host: inconsistent totals from the device");
+    }
+    if (copied) FS_HIP_DRAIN(ctx, hipMemcpyAsync(payload, ctx->co_d_payload, copied, hipMemcpyDeviceToHost, ks));
+    if (t.n_runs) FS_HIP_DRAIN(ctx, hipMemcpyAsync(runs, d_runs, (size_t)t.n_runs * sizeof(fs_rx_run), hipMemcpyDeviceToHost, ks));
+    if (flows && t.n_flows)
+        FS_HIP_DRAIN(ctx, hipMemcpyAsync(flows, d_flows, (size_t)t.n_flows * sizeof(fs_rx_flow), hipMemcpyDeviceToHost, ks));
+    if (t.n_accepted) FS_HIP_DRAIN(ctx, hipMemcpyAsync(order, d_order, (size_t)t.n_accepted * 4, hipMemcpyDeviceToHost, ks));
+    if (run_of) FS_HIP_DRAIN(ctx, hipMemcpyAsync(run_of, d_run_of, (size_t)n * 4, hipMemcpyDeviceToHost, ks));
+    if (out) FS_HIP_DRAIN(ctx, hipMemcpyAsync(out, sl.d_out, (size_t)n * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
+    if (status) FS_HIP_DRAIN(ctx, hipMemcpyAsync(status, sl.d_status, n, hipMemcpyDeviceToHost, ks));
+    FS_HIP_DRAIN(ctx, hipEventRecord(sl.consumed, ks));
+    sl.used = true;
+    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
+    ctx->host_dirty = false;
+    *totals = t;
+    return FS_SUCCESS;
+}
+
 fs_status fs_digest_batch_multi(fs_ctx* const* ctxs, int nctx, const uint8_t* frames, uint64_t frames_bytes,
                                 const uint64_t* offsets, const uint32_t* lengths, uint32_t n, uint32_t mtu,
                                 fs_digest* out, uint8_t* status) {
@@ -1238,6 +1390,21 @@ fs_status fs_test_set_kernel_exact(fs_ctx* ctx, int force) {
 // ... and which path the latest fs_digest_batch_host took: 1 staged in one chunk, 2 read in place,
 // 3 chunked (0 before the first call).
 int fs_test_last_host_path(const fs_ctx* ctx) { return ctx ? ctx->last_host_path : -1; }
+// ... the flow table's hash ANDed with `mask` before it becomes a slot index (0: every key starts at
+// slot 0, so every insert probes linearly; the results of fs_coalesce_flows_batch do not change).
+fs_status fs_test_set_flow_hash_mask(fs_ctx* ctx, uint32_t mask) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->flow_hash_mask = mask;
+    return FS_SUCCESS;
+}
+// ... and which groups of fs_coalesce_flows_batch's launches a call enqueues (kFlowStep* bits,
+// framesum_internal.h; anything but all of them also leaves the digest launch out): 2 repeats the
+// sort alone on the keys the call before left in the context's scratch, for tools/coalesce_bench.py.
+fs_status fs_test_set_flow_steps(fs_ctx* ctx, uint32_t steps) {
+    if (!ctx || steps == 0 || (steps & ~framesum::kFlowStepsAll)) return FS_E_INVALID;
+    ctx->flow_steps = steps;
+    return FS_SUCCESS;
+}
 #endif
 
 fs_status fs_host_alloc(fs_ctx* ctx, uint64_t bytes, void** out) {

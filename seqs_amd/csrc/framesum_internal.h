@@ -100,4 +100,23 @@ hipError_t launch_coalesce(const uint8_t* frames, const uint64_t* offsets, const
                            uint32_t* run_of, fs_rx_totals* totals, uint8_t* scratch, int max_workgroups,
                            hipStream_t stream);
 
+// ---- Flow-aware RX coalesce (framesum_flows.hip). The launches that follow a batch's digest launch
+// on `stream` (fs_coalesce_flows_batch in include/framesum.h): the delivery order (keys, flow table,
+// sort keys), the sort, and the scans and the copy over delivery slots. `scratch`: `s.bytes` of device
+// memory, 256-byte aligned, `s` = flows_scratch(n) (which asks the sort for its temporary storage's
+// size, so callers compute it once per call). `hash_mask` is ANDed with a key's hash (all ones in
+// the product). `steps`: which of the three groups to enqueue, all of them in every call of the ABI;
+// the test library times the sort alone on the keys an earlier call has left.
+struct FlowScratch {
+    uint64_t keys, sk_in, sorted, rec, payoff, partial, prefix, copied, table, rep, slot_of, runidx, hidx, flowidx, fhidx,
+        sort_temp, sort_bytes, bytes;
+};
+constexpr uint32_t kFlowStepOrder = 1, kFlowStepSort = 2, kFlowStepGather = 4, kFlowStepsAll = 7;
+FlowScratch flows_scratch(uint32_t n);
+hipError_t launch_coalesce_flows(const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
+                                 uint32_t flags, const uint8_t* status, uint8_t* payload, uint64_t payload_cap,
+                                 fs_rx_run* runs, fs_rx_flow* flows_out, uint32_t* order, uint32_t* run_of,
+                                 fs_rx_flow_totals* totals, uint8_t* scratch, const FlowScratch& s, uint32_t hash_mask,
+                                 int max_workgroups, uint32_t steps, hipStream_t stream);
+
 }  // namespace framesum

@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "fs_segment_batch_host",
     "fs_coalesce_batch",
     "fs_coalesce_batch_host",
+    "fs_coalesce_flows_batch",
+    "fs_coalesce_flows_batch_host",
     "fs_digest_batch_multi",
     "fs_ctx_set_kernel",
     "fs_ctx_set_workgroups",
@@ -97,6 +99,11 @@ SEGMENT_MAX_FRAMES = 4096
 RUN_DTYPE = np.dtype([("payload_off", "<u8"), ("payload_len", "<u4"), ("first_frame", "<u4"), ("n_frames", "<u4"),
                       ("tcp_flags", "u1"), ("reserved", "u1", (3,))])
 TOTALS_DTYPE = np.dtype([("payload_bytes", "<u8"), ("n_runs", "<u4"), ("reserved", "<u4")])
+# fs_rx_flow: one flow of the flow-aware RX coalesce (32 bytes, no padding), and fs_rx_flow_totals (24 bytes)
+FLOW_DTYPE = np.dtype([("payload_off", "<u8"), ("payload_len", "<u8"), ("first_run", "<u4"), ("n_runs", "<u4"),
+                       ("first_frame", "<u4"), ("n_frames", "<u4")])
+FLOW_TOTALS_DTYPE = np.dtype([("payload_bytes", "<u8"), ("n_runs", "<u4"), ("n_flows", "<u4"), ("n_accepted", "<u4"),
+                              ("reserved", "<u4")])
 
 
 class FramesumError(RuntimeError):
@@ -161,6 +168,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.fs_coalesce_batch.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp]
     lib.fs_coalesce_batch_host.restype = i32
     lib.fs_coalesce_batch_host.argtypes = [vp, vp, u64, vp, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp]
+    lib.fs_coalesce_flows_batch.restype = i32
+    lib.fs_coalesce_flows_batch.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.fs_coalesce_flows_batch_host.restype = i32
+    lib.fs_coalesce_flows_batch_host.argtypes = [vp, vp, u64, vp, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "fs_ctx_set_workgroups"):  # (absent from builds before round 4: same-box A/B runs)
         lib.fs_ctx_set_workgroups.restype = i32
         lib.fs_ctx_set_workgroups.argtypes = [vp, ctypes.c_int]
@@ -198,6 +209,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.fs_test_set_kernel_exact.argtypes = [vp, ctypes.c_int]
         lib.fs_test_last_host_path.restype = ctypes.c_int
         lib.fs_test_last_host_path.argtypes = [vp]
+        lib.fs_test_set_flow_hash_mask.restype = i32
+        lib.fs_test_set_flow_hash_mask.argtypes = [vp, u32]
+        lib.fs_test_set_flow_steps.restype = i32
+        lib.fs_test_set_flow_steps.argtypes = [vp, u32]
     _libs[p] = lib
     if path is None:
         _lib = lib
@@ -555,6 +570,89 @@ class Engine:
         return [(int(r["first_frame"]), int(r["n_frames"]), int(r["tcp_flags"]),
                  bytes(payload[int(r["payload_off"]) : int(r["payload_off"]) + int(r["payload_len"])])) for r in runs]
 
+    # ---- flow-aware RX coalesce ----------------------------------------------
+    def coalesce_flows_device(self, frames, offsets, lengths, mtu: int = 0, flags: int = 0, payload=None, stream=None):
+        """coalesce_device for batches in which the segments of several flows interleave
+        (fs_coalesce_flows_batch): the accepted frames are grouped by flow (protocol, addresses,
+        ports), `payload` receives each flow's payload contiguously, flows in the order of their
+        first frames, and the runs are found inside each flow. Returns (payload, runs, flows, order,
+        run_of, totals, out, status) device tensors: runs (n, 24) uint8 = RUN_DTYPE records whose
+        first_frame indexes `order`, flows (n, 32) uint8 = FLOW_DTYPE records, order (n,) int32 of
+        which the first n_accepted are written (the batch indices in delivery order), run_of (n,)
+        int32, totals (24,) uint8 = one FLOW_TOTALS_DTYPE record. Asynchronous on `stream`;
+        split_flows() brings the records to the host."""
+        import torch
+
+        n, out, status, stream = self._device_args(frames, offsets, lengths, None, None, stream)
+        dev = frames.device
+        if payload is None:
+            payload = torch.empty((frames.numel(),), dtype=torch.uint8, device=dev)
+        assert payload.is_cuda and payload.dtype == torch.uint8 and payload.is_contiguous()
+        runs = torch.empty((n, RUN_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        flows = torch.empty((n, FLOW_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        order = torch.empty((n,), dtype=torch.int32, device=dev)
+        run_of = torch.empty((n,), dtype=torch.int32, device=dev)
+        totals = torch.empty((FLOW_TOTALS_DTYPE.itemsize,), dtype=torch.uint8, device=dev)
+        vp = ctypes.c_void_p
+        st = self.lib.fs_coalesce_flows_batch(
+            self._ctx, vp(frames.data_ptr()), vp(offsets.data_ptr()), vp(lengths.data_ptr()), n, mtu, flags,
+            vp(payload.data_ptr()), int(payload.numel()), vp(runs.data_ptr()), vp(flows.data_ptr()), vp(order.data_ptr()),
+            vp(run_of.data_ptr()), vp(totals.data_ptr()), vp(out.data_ptr()), vp(status.data_ptr()),
+            vp(stream.cuda_stream))
+        self._check(st, "fs_coalesce_flows_batch")
+        return payload, runs, flows, order, run_of, totals, out, status
+
+    def coalesce_flows_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, mtu: int = 0,
+                            flags: int = 0, payload: Optional[np.ndarray] = None):
+        """coalesce_flows_device from and to host memory (fs_coalesce_flows_batch_host). Returns
+        (payload, runs RUN_DTYPE[n_runs], flows FLOW_DTYPE[n_flows], order uint32[n_accepted], run_of
+        uint32, totals FLOW_TOTALS_DTYPE scalar record, digests, status) numpy arrays."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        n = int(lengths.size)
+        assert offsets.size == n, "offsets and lengths must describe the same frames"
+        if payload is None:
+            payload = np.zeros(int(lengths.sum(dtype=np.uint64)), dtype=np.uint8)
+        assert payload.dtype == np.uint8 and payload.flags["C_CONTIGUOUS"] and payload.flags["WRITEABLE"]
+        runs = np.zeros(n, dtype=RUN_DTYPE)
+        flows = np.zeros(n, dtype=FLOW_DTYPE)
+        order = np.zeros(n, dtype=np.uint32)
+        run_of = np.zeros(n, dtype=np.uint32)
+        totals = np.zeros(1, dtype=FLOW_TOTALS_DTYPE)
+        out = np.zeros(n, dtype=DIGEST_DTYPE)
+        status = np.zeros(n, dtype=np.uint8)
+        vp = ctypes.c_void_p
+        st = self.lib.fs_coalesce_flows_batch_host(
+            self._ctx, frames.ctypes.data_as(vp), frames.nbytes, offsets.ctypes.data_as(vp), lengths.ctypes.data_as(vp), n,
+            mtu, flags, payload.ctypes.data_as(vp), payload.nbytes, runs.ctypes.data_as(vp), flows.ctypes.data_as(vp),
+            order.ctypes.data_as(vp), run_of.ctypes.data_as(vp), totals.ctypes.data_as(vp), out.ctypes.data_as(vp),
+            status.ctypes.data_as(vp))
+        self._check(st, "fs_coalesce_flows_batch_host")
+        t = totals[0]
+        return (payload, runs[: int(t["n_runs"])], flows[: int(t["n_flows"])], order[: int(t["n_accepted"])], run_of, t,
+                out, status)
+
+    def coalesce_flows_batch(self, frames: Sequence[bytes], mtu: int = 0) -> list:
+        """The reference's RX demultiplexing and delivery for many frames (findPort,
+        stacks/portstack.go:309 and :246; TCPConn.recv, stacks/tcpconn.go:347-369): per flow, in the
+        order of the flows' first frames, (proto, src, dst, sport, dport, [(tcp_flags, payload_bytes)
+        per run]) with src and dst the 4 address bytes."""
+        if len(frames) == 0:
+            return []
+        buf, offsets, lengths = pack_frames(frames, 1)
+        payload, runs, flows, order, _, _, _, _ = self.coalesce_flows_host(buf, offsets, lengths, mtu)
+        res = []
+        for fl in flows:
+            f = frames[int(order[int(fl["first_frame"])])]
+            l4 = 14 + 4 * (f[14] & 15)
+            rs = runs[int(fl["first_run"]) : int(fl["first_run"]) + int(fl["n_runs"])]
+            res.append((f[23], bytes(f[26:30]), bytes(f[30:34]), int.from_bytes(f[l4 : l4 + 2], "big"),
+                        int.from_bytes(f[l4 + 2 : l4 + 4], "big"),
+                        [(int(r["tcp_flags"]),
+                          bytes(payload[int(r["payload_off"]) : int(r["payload_off"]) + int(r["payload_len"])])) for r in rs]))
+        return res
+
     # ---- host-staged path (numpy in, numpy out) -----------------------------
     def host_empty(self, shape, dtype=np.uint8) -> np.ndarray:
         """A numpy array in pinned host memory (fs_host_alloc), freed with the array."""
@@ -707,6 +805,17 @@ def split_runs(runs, totals):
     k = int(t["n_runs"])
     r = np.ascontiguousarray(runs[:k].cpu().numpy()).reshape(-1).view(RUN_DTYPE)
     return r, int(t["payload_bytes"]), k
+
+
+def split_flows(runs, flows, order, totals):
+    """The host view of coalesce_flows_device's `runs`, `flows`, `order` and `totals` tensors (this
+    waits for them): (RUN_DTYPE[n_runs], FLOW_DTYPE[n_flows], order uint32[n_accepted], the
+    FLOW_TOTALS_DTYPE record)."""
+    t = np.ascontiguousarray(totals.cpu().numpy()).view(FLOW_TOTALS_DTYPE)[0]
+    r = np.ascontiguousarray(runs[: int(t["n_runs"])].cpu().numpy()).reshape(-1).view(RUN_DTYPE)
+    f = np.ascontiguousarray(flows[: int(t["n_flows"])].cpu().numpy()).reshape(-1).view(FLOW_DTYPE)
+    o = np.ascontiguousarray(order[: int(t["n_accepted"])].cpu().numpy()).view(np.uint32)
+    return r, f, o, t
 
 
 def shard_count(n: int, nshards: int, shard: int) -> int:

@@ -12,7 +12,16 @@ frame and payload buffers (more than the 256 MiB Infinity Cache holds in total):
 twice and the payload is written once. The goal is (a) <= 1.5 x ((b) + (c)).
 Prints the per-round medians, the medians over rounds and one JSON line.
 
-    python tools/coalesce_bench.py [--rounds 3] [--launches 100] [--buffers 4] [--out FILE]
+With --flows F the same 65,536 frames come from F sends of 65,536 / F frames each, and a second set of
+`offsets` / `lengths` lists them round-robin across the sends (A0 B0 ... A1 B1 ...; no bytes move).
+Then five things are timed the same way:
+  (a) fs_coalesce_flows_batch on the interleaved descriptors;
+  (b) fs_coalesce_batch on the same frames un-interleaved;
+  (c) the flow coalesce's sort alone (through the test library's fs_test_set_flow_steps, on the keys
+      a whole call has left in the context's scratch);
+  and the digest and the copy as above. The report states (a) / (b).
+
+    python tools/coalesce_bench.py [--flows F] [--rounds 3] [--launches 100] [--buffers 4] [--out FILE]
 """
 import argparse
 import ctypes
@@ -42,6 +51,7 @@ def main() -> None:
     p.add_argument("--frames", type=int, default=65536)
     p.add_argument("--frames-per-send", type=int, default=44)
     p.add_argument("--mss", type=int, default=1446)
+    p.add_argument("--flows", type=int, default=0, help="F sends, their frames interleaved round-robin (0: off)")
     p.add_argument("--out", default=None, help="also write the report to this file")
     a = p.parse_args()
 
@@ -49,7 +59,13 @@ def main() -> None:
 
     assert torch.cuda.is_available(), "needs a GPU"
     torch.cuda.init()
-    from seqs_amd import RUN_DTYPE, SEND_DTYPE, TOTALS_DTYPE, Engine, segment_layout, split_runs
+    from seqs_amd import (FLOW_DTYPE, FLOW_TOTALS_DTYPE, RUN_DTYPE, SEND_DTYPE, TOTALS_DTYPE, Engine, segment_layout,
+                          split_flows, split_runs)
+    from seqs_amd.framesum import TEST_LIB_PATH
+
+    if a.flows:
+        assert a.frames % a.flows == 0 and a.frames // a.flows <= 4096, "--flows must divide --frames into sends of <= 4096"
+        a.frames_per_send = a.frames // a.flows
 
     dev = torch.device("cuda:0")
     # the HIP runtime this process already runs on (the one torch and the library loaded), by its path
@@ -121,6 +137,47 @@ def main() -> None:
 
     kinds = [("coalesce", run_coalesce), ("digest", run_digest), ("copy", run_copy)]
 
+    if a.flows:
+        # the interleaved descriptors: frame k of the batch is frame k // F of send k % F
+        k = torch.arange(n_frames, device=dev)
+        perm = (k % a.flows) * a.frames_per_send + k // a.flows
+        inter = [(built[b][1][perm].contiguous(), built[b][2][perm].contiguous()) for b in range(a.buffers)]
+        flows_t = torch.empty((n_frames, FLOW_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        order_t = torch.empty((n_frames,), dtype=torch.int32, device=dev)
+        ftotals = torch.empty((FLOW_TOTALS_DTYPE.itemsize,), dtype=torch.uint8, device=dev)
+
+        def flow_args(ctx, b):
+            return (ctx, vp(frames[b].data_ptr()), vp(inter[b][0].data_ptr()), vp(inter[b][1].data_ptr()), n_frames, 0, 0,
+                    vp(gathered[b].data_ptr()), payload_bytes, vp(runs.data_ptr()), vp(flows_t.data_ptr()),
+                    vp(order_t.data_ptr()), vp(run_of.data_ptr()), vp(ftotals.data_ptr()), vp(out.data_ptr()),
+                    vp(status.data_ptr()), vp(stream.cuda_stream))
+
+        fl_args = [flow_args(eng._ctx, b) for b in range(a.buffers)]
+        teng = Engine(0, lib_path=TEST_LIB_PATH)  # (c): its context's scratch keeps the sort keys of one whole call
+        t_args = flow_args(teng._ctx, 0)
+
+        def run_flows(b):
+            st = eng.lib.fs_coalesce_flows_batch(*fl_args[b])
+            assert st == 0, eng.lib.fs_last_error(eng._ctx)
+
+        def run_sort(b):
+            st = teng.lib.fs_coalesce_flows_batch(*t_args)
+            assert st == 0, teng.lib.fs_last_error(teng._ctx)
+
+        # each send's payload comes back contiguous, one flow and one run per send: checked once
+        gathered[0].zero_()
+        with torch.cuda.stream(stream):
+            run_flows(0)
+            run_sort(0)
+        stream.synchronize()
+        fr, ff, fo, ft = split_flows(runs, flows_t, order_t, ftotals)
+        assert (int(ft["payload_bytes"]), int(ft["n_runs"]), int(ft["n_flows"]), int(ft["n_accepted"])) == \
+            (payload_bytes, n_sends, n_sends, n_frames) and torch.equal(gathered[0], src)
+        assert np.array_equal(fr["n_frames"], counts.astype(np.uint32)) and np.array_equal(perm.cpu().numpy()[fo], np.arange(n_frames))
+        assert teng.lib.fs_test_set_flow_steps(teng._ctx, 2) == 0  # from here on the test context only sorts
+        kinds = [("flows", run_flows), ("coalesce", run_coalesce), ("sort", run_sort), ("digest", run_digest),
+                 ("copy", run_copy)]
+
     def timed(fn, launches):
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(launches)]
         with torch.cuda.stream(stream):
@@ -154,6 +211,13 @@ def main() -> None:
     lines.append(f"median of rounds: (a) coalesce {med['coalesce']:.2f} us  (b) digest {med['digest']:.2f} us  "
                  f"(c) copy {med['copy']:.2f} us  (b)+(c) {floor:.2f} us  (a) / ((b)+(c)) = {ratio:.3f}  "
                  f"goal <= 1.5: {'met' if res['goal_met'] else 'MISSED'}")
+    if a.flows:
+        spread = {k: round(max(v) - min(v), 2) for k, v in rounds.items()}
+        res.update({"flows": a.flows, "flows_us": round(med["flows"], 2), "sort_us": round(med["sort"], 2),
+                    "flows_over_coalesce": round(med["flows"] / med["coalesce"], 3), "round_spread_us": spread})
+        lines.append(f"--flows {a.flows}: (a) coalesce_flows {med['flows']:.2f} us  (b) coalesce, un-interleaved "
+                     f"{med['coalesce']:.2f} us  (c) sort alone {med['sort']:.2f} us  (a) / (b) = {med['flows'] / med['coalesce']:.3f}")
+        teng.close()
     lines.append(json.dumps(res))
     text = "\n".join(lines)
     print(text)
