@@ -246,6 +246,13 @@ fs_status fs_segment_batch_host(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n
  * listed in order of first_frame: runs[0 .. totals->n_runs) are written, the entries beyond are not.
  * run_of[i] (nullable) is frame i's run index, or 0xFFFFFFFF for a frame that was not accepted.
  *
+ * A run longer than 4 GiB: the join rule compares Seq modulo 2^32, so a chain may carry 2^32 bytes or
+ * more (at least 65,592 frames), which the 32-bit fs_rx_run.payload_len cannot hold. Such a run is not
+ * broken: its payload_len is its length modulo 2^32, and everything else stays exact: n_frames, the
+ * payload itself, the next run's payload_off (so a run's length is also next.payload_off -
+ * payload_off, or totals->payload_bytes - payload_off for the last run), fs_rx_flow.payload_len (64-bit)
+ * and the totals. A caller that can meet such runs takes the length from there.
+ *
  * FS_E_INVALID, checked on the host before any device work: a null ctx, frames, offsets, lengths,
  * runs or totals; a null payload with payload_cap not 0; flags other than 0 or FS_RX_FCS; n above
  * 2^31; frames not 4-byte aligned (as fs_digest_batch). n of 0 is success: it writes zero totals and
@@ -261,7 +268,7 @@ fs_status fs_segment_batch_host(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n
 
 typedef struct fs_rx_run {  /* 24 bytes, no padding */
     uint64_t payload_off;   /* the run's bytes are payload[payload_off : payload_off + payload_len) */
-    uint32_t payload_len;
+    uint32_t payload_len;   /* modulo 2^32 for a run of 4 GiB or more (above); payload_off is always exact */
     uint32_t first_frame;   /* batch index of the run's first frame */
     uint32_t n_frames;      /* frames first_frame .. first_frame + n_frames - 1, all accepted */
     uint8_t tcp_flags;      /* TCP: first frame's flags byte | (last frame's FIN, PSH); UDP: 0 */

@@ -85,7 +85,7 @@ def expected(buf: np.ndarray, offsets, lengths, mtu: int, flags: int, noise: np.
         if prev is not None and joins(prev, f):
             r = runs[-1]
             r["n_frames"] += 1
-            r["payload_len"] += e - s
+            r["payload_len"] = (r["payload_len"] + e - s) % (1 << 32)  # a run past 4 GiB: its length modulo 2^32
             r["tcp_flags"] |= f[47] & (FIN | PSH)
         else:
             l4 = 14 + (f[14] & 15) * 4

@@ -114,6 +114,93 @@ static void check_multi(const Batch& b, int nctx) {
     }
 }
 
+// A batch moved up by `base` bytes (the buffer grows by as much), and one whose odd frames alone move
+// up: offsets then alternate between the two sides of `base`, unordered.
+static Batch moved(Batch b, uint64_t base, bool odd_only = false) {
+    for (size_t i = 0; i < b.off.size(); ++i)
+        if (!odd_only || (i & 1)) b.off[i] += base;
+    b.bytes += base;
+    return b;
+}
+
+// Offsets around and above 2^32 (the ABI's offsets are 64-bit so that batches beyond 4 GiB work): the
+// same invariants as below 2^32, and the exact values of the span arithmetic.
+static void check_high_offsets(std::mt19937_64& rng) {
+    const uint64_t G = uint64_t(1) << 32;
+    for (int kind = 0; kind < 5; ++kind)
+        for (uint32_t n : {1u, 2u, 65u, 1000u})
+            for (uint64_t cb : {uint64_t(4096), uint64_t(16) << 20}) {
+                const Batch b = make_batch(rng, n, kind);
+                const uint64_t span = std::min<uint64_t>(b.bytes - 16, G);  // (a sparse batch can be longer)
+                // lo above 2^32; the span crossing 2^32 (in its middle, one byte in, one byte before its
+                // end); the two sides alternating
+                for (uint64_t base : {G + 12345 * 4, G + 1, 3 * G - 4, G - span / 2, G - 1, G - (span ? span - 1 : 0)}) {
+                    check_chunks(moved(b, base), cb, kind == 0 ? 100u : (1u << 20));
+                    for (int nctx : {1, 2, 3}) check_multi(moved(b, base), nctx);
+                }
+                check_chunks(moved(b, G + 4096, true), cb, 1u << 20);
+                for (int nctx : {2, 3}) check_multi(moved(b, G + 4096, true), nctx);
+            }
+    {   // scan_batch and first_frame_out_of_range with every number above 2^32
+        std::vector<uint64_t> off = {G + 500, G + 100, 3 * G + 7, G + 50};
+        std::vector<uint32_t> len = {10, 20, 10, 10};
+        const Scan sc = scan_batch(off.data(), len.data(), 4, 3 * G + 17);
+        CHECK(sc.bad == 4 && sc.lo == G + 50 && sc.hi == 3 * G + 17 && sc.max_len == 20 && sc.min_len == 10);
+        CHECK(scan_batch(off.data(), len.data(), 4, 3 * G + 16).bad == 2);  // one byte past the buffer
+        CHECK(first_frame_out_of_range(off.data(), len.data(), 4, 3 * G + 17) == 4);
+        CHECK(first_frame_out_of_range(off.data(), len.data(), 4, 3 * G + 16) == 2);
+        CHECK(first_frame_out_of_range(off.data(), len.data(), 4, 3 * G + 20, 4) == 2);  // ... with the FCS room
+        CHECK(scan_batch(off.data(), len.data(), 4, 3 * G + 20, 4).bad == 2);
+        CHECK(scan_batch(off.data(), len.data(), 4, 3 * G + 21, 4).bad == 4);
+        CHECK(scan_batch(off.data(), len.data(), 2, G + 509).bad == 0);
+        CHECK(scan_batch(off.data(), len.data(), 2, G + 510).bad == 2);
+        // a buffer that ends below 2^32 holds none of them, whatever their low halves say
+        CHECK(scan_batch(off.data(), len.data(), 4, 100000).bad == 0);
+        CHECK(first_frame_out_of_range(off.data() + 1, len.data() + 1, 3, G - 1) == 0);
+        // offsets near 2^64: offset + length wraps to a small number and must not pass the range check
+        std::vector<uint64_t> wrap = {G + 5, UINT64_MAX - 2, G + 9, UINT64_MAX - (G - 1) + 3, UINT64_MAX};
+        std::vector<uint32_t> wlen = {10, 10, 10, UINT32_MAX, 1};
+        CHECK(scan_batch(wrap.data(), wlen.data(), 5, G + 1000).bad == 1);
+        CHECK(first_frame_out_of_range(wrap.data(), wlen.data(), 5, G + 1000) == 1);
+        CHECK(scan_batch(wrap.data() + 2, wlen.data() + 2, 3, G + 1000).bad == 1);
+        CHECK(scan_batch(wrap.data() + 4, wlen.data() + 4, 1, UINT64_MAX).bad == 0);  // (the per-frame fall-back)
+        CHECK(scan_batch(wrap.data() + 4, wlen.data() + 4, 1, UINT64_MAX - 1).bad == 0);
+        CHECK(scan_batch(wrap.data() + 1, wlen.data() + 1, 1, UINT64_MAX).bad == 0);
+    }
+    {   // copy_span: exact values on both sides of 2^32
+        uint64_t lo = 0, hi = 0;
+        copy_span(G + 17, G + 101, G + 4096, lo, hi);
+        CHECK(lo == G && hi == G + 104);
+        copy_span(G + 15, G + 101, G + 102, lo, hi);  // the prefix reaches back below 2^32; the end is capped
+        CHECK(lo == G - 16 && hi == G + 102);
+        copy_span(G - 3, G + 1, G + 4096, lo, hi);  // a frame across 2^32
+        CHECK(lo == G - 32 && hi == G + 4);
+        copy_span(G - 100, G - 1, 2 * G, lo, hi);  // the end rounds up onto 2^32
+        CHECK(lo == G - 128 && hi == G);
+        copy_span(5 * G + 16, 5 * G + 16, 6 * G, lo, hi);  // an empty span far up
+        CHECK(lo == 5 * G && hi == 5 * G + 16);
+        copy_span(3, 2 * G + 1, 2 * G + 2, lo, hi);  // a span longer than 4 GiB
+        CHECK(lo == 0 && hi == 2 * G + 2);
+    }
+    {   // host_chunks: two clusters 4 GiB apart, 70 frames each, chunks of 64 KiB: no chunk spans both
+        Batch b;
+        for (uint32_t i = 0; i < 140; ++i) {
+            b.off.push_back((i < 70 ? G + 4096 : 64) + 128 * (i % 70));
+            b.len.push_back(100);
+        }
+        b.bytes = G + 4096 + 128 * 70;
+        check_chunks(b, 65536, 1u << 20);
+        std::vector<Chunk> ch;
+        host_chunks(b.off.data(), b.len.data(), 140, b.bytes, 65536, 1u << 20, ch);
+        CHECK(ch.size() == 2 && ch[0].c1 == 70 && ch[0].cpy_lo == G + 4096 - 16 && ch[0].cpy_hi == G + 4096 + 128 * 69 + 100);
+        CHECK(ch.size() == 2 && ch[1].cpy_lo == 48 && ch[1].cpy_hi == 64 + 128 * 69 + 100);
+        // multi_blocks puts them in buffer order: the low cluster first, and cuts between the clusters
+        MultiPlan p;
+        multi_blocks(b.off.data(), b.len.data(), 140, 2, p);
+        CHECK(p.order.size() == 140 && p.frame(0) == 70 && p.frame(69) == 139 && p.frame(70) == 0 && p.cut[1] == 70);
+    }
+}
+
 static void check_shards(uint64_t n, uint32_t N) {
     uint64_t sum = 0;
     for (uint32_t k = 0; k < N; ++k) sum += shard_count(n, N, k);
@@ -267,6 +354,7 @@ int main() {
         CHECK(scan_batch(off.data(), len.data(), 1, 14, 4).bad == 1);
         CHECK(scan_batch(off.data(), len.data(), 0, 14).bad == 0);
     }
+    check_high_offsets(rng);
     // multi blocks: more contexts than frames, empty batches, unordered and overlapping batches
     for (int kind = 0; kind < 5; ++kind)
         for (uint32_t n : {0u, 1u, 3u, 8u, 9u, 100u, 4097u})

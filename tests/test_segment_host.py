@@ -54,6 +54,24 @@ def test_layout_agrees_with_restatement():
     assert framesum.segment_layout(np.zeros(0, dtype=framesum.SEND_DTYPE), 0, 4) == (0, 0)
 
 
+def test_layout_beyond_4_gib():
+    # the layout tests/test_gpu_large_offsets.py builds on the device: its slots pass 2^32
+    from test_gpu_large_offsets import big_layout
+
+    for flags in (0, 2):
+        sends, lens, offs, total, first, _ = big_layout(flags)
+        assert total > 1 << 32 and int(offs.max()) >= 1 << 32
+        assert framesum.segment_layout(sends, flags, 4096) == (lens.size, total)
+        # the per-send bases are exact: the layout of the first k sends ends where send k begins
+        for k in (1, int(np.searchsorted(offs[first[:-1]], 1 << 32)), sends.size - 1):
+            assert framesum.segment_layout(sends[:k], flags, 4096) == (int(first[k]), int(offs[first[k]]))
+            assert int(offs[first[k]]) == int(first[k]) * 4096
+        k = int(np.searchsorted(offs[first[:-1]], 1 << 32))
+        assert int(offs[first[k - 1]]) < 1 << 32 <= int(offs[first[k]])
+    # with align 1 the same sends stay far below 2^32: the slots, not the bytes, carry the layout up
+    assert framesum.segment_layout(sends, 0, 1)[1] == int(lens.sum()) < 1 << 28
+
+
 def test_send_dtype_is_the_c_struct():
     d = framesum.SEND_DTYPE
     assert d.itemsize == 72
