@@ -1,124 +1,42 @@
-// framesum C ABI (include/framesum.h) — context management, device-resident and
-// host-staged batch entry points. No CPU fallback: every digest is computed by
-// the gfx950 kernel (framesum_kernel.hip); a missing/unsupported device is an error.
+// framesum C ABI (include/framesum.h) -- context lifecycle, the device-resident and host-staged
+// digest and fill calls, fs_digest_batch_multi, the setters and the test library's hooks; and the
+// definitions of what framesum_ctx.h shares with the TX frame build (framesum_api_tx.cpp) and the RX
+// coalesce (framesum_api_rx.cpp). No CPU fallback: every digest is computed by the gfx950 kernel
+// (framesum_kernel.hip); a missing/unsupported device is an error.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <new>
-#include <system_error>
 #include <string>
+#include <system_error>
 #include <thread>
 #include <vector>
 
-#include "../../include/framesum.h"
-#include "framesum_flows.h"
-#include "framesum_internal.h"
-#include "framesum_plan.h"
-#include "framesum_segment.h"
+#include "framesum_ctx.h"
 
 using framesum::FsTables;
+using namespace framesum::host;
 
-// Host-staged path: the batch is cut into chunks of about kChunkBytes of frame bytes,
-// staged through kHostSlots device buffers. The whole batch's descriptors go first, in one
-// H2D copy; the chunks' frame bytes then alternate between two copy streams (two DMA queues
-// keep the PCIe link busier than one: no gap between one chunk's copy and the next); kernels
-// and the small D2H copies run on a compute stream. Events order each chunk's kernel after
-// its copy (`copied`) and the reuse of a slot by chunk c + kHostSlots after chunk c's kernel
-// (`consumed`), so chunk c+1's H2D overlaps chunk c's kernel and D2H.
-constexpr int kHostSlots = 3;
-constexpr uint64_t kChunkBytes = 16ull << 20;
-constexpr uint32_t kChunkFrames = 1u << 20;
-// Frames per call: tile and frame indices are 32-bit in the kernel (n + 15 must not wrap).
-constexpr uint32_t kMaxFrames = 1u << 31;
+// At least `bytes` + 256 bytes. A buffer in use by queued work is safe to regrow without a wait of
+// its own: hipFree synchronizes the device before it releases the memory (only a staging slot waits
+// first, for its `consumed` event: ensure_slot).
+fs_status DevBuf::grow(fs_ctx* ctx, uint64_t bytes, const char* what) {
+    if (bytes <= cap) return FS_SUCCESS;
+    release();
+    if (hipMalloc(&p, bytes + 256) != hipSuccess) return set_err(ctx, FS_E_NOMEM, what);
+    cap = bytes + 256;
+    return FS_SUCCESS;
+}
 
-struct HostSlot {
-    hipEvent_t copied = nullptr, consumed = nullptr, landed = nullptr;  // landed: the chunk's results are in the mirror
-    bool used = false;
-    uint8_t* d_frames = nullptr;
-    uint64_t cap_frames = 0;
-    uint64_t* d_offsets = nullptr;
-    uint32_t* d_lengths = nullptr;
-    fs_digest* d_out = nullptr;
-    uint8_t* d_status = nullptr;
-    uint32_t cap_n = 0;
-};
+void DevBuf::release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+}
 
-// fs_segment_batch stages each call's sends in a block of its own: pinned host memory the call
-// fills, a device copy the kernel reads, and an event recorded behind the kernel. A block is
-// refilled only once its event has completed, so calls need no synchronization between them.
-constexpr int kSegStages = 32;
-struct SegStage {
-    uint8_t* h = nullptr;
-    uint8_t* d = nullptr;
-    uint64_t cap = 0;
-    hipEvent_t done = nullptr;
-    bool used = false;
-};
-
-struct fs_ctx {
-    int device = 0;
-    int num_cus = 0;
-    FsTables* d_tables = nullptr;
-    // fault injection for the host-staged pipeline's tests, settable only through the test
-    // library's fs_test_set_fault (-DFS_TEST_HOOKS): fs_digest_batch_host fails with FS_E_NOMEM at
-    // chunk k, after the earlier chunks' work and chunk k's copy are queued. -1 in the product.
-    long fault_chunk = -1;
-    // the path the latest fs_digest_batch_host took (fs_test_last_host_path): 1 staged in one
-    // chunk, 2 read in place, 3 chunked
-    int last_host_path = 0;
-    // the host-mapped block the kernels post their reports to (framesum_choice.h), and what the
-    // context remembers of them between launches
-    volatile uint32_t* h_report = nullptr;
-    uint32_t* d_report = nullptr;
-    framesum::ChoiceState choice;
-    int force_kernel = 0;  // fs_ctx_set_kernel
-    int workgroups = 0;    // fs_ctx_set_workgroups (0: one per CU)
-    HostSlot slot[kHostSlots];
-    hipStream_t copy_stream = nullptr, compute_stream = nullptr;
-    hipStream_t copy_stream2 = nullptr;  // the odd chunks' frame copies
-    hipEvent_t desc_copied = nullptr;    // the batch's descriptors are on the device
-    hipEvent_t host_done = nullptr;      // a host-staged call's last device work (polled, host_wait)
-    // a host-staged call left work in flight (it failed half-way): the next one drains the
-    // context's streams first (quiesce_host_streams); a call that returns FS_SUCCESS leaves none
-    bool host_dirty = false;
-    uint8_t* d_desc = nullptr;           // the batch's offsets (8 n) then lengths (4 n)
-    uint64_t cap_desc_n = 0;
-    // pinned host mirrors of the descriptors and results, so every per-chunk copy is
-    // asynchronous even when the caller's arrays are pageable (Go slices, numpy)
-    uint8_t* h_pin = nullptr;
-    uint8_t* d_pin = nullptr;  // h_pin as the device addresses it (mapped): kernels write results there
-    uint64_t cap_pin_n = 0;
-    // TX frame build: the kernel's table basis (built on the first call), the staging blocks, and
-    // the device buffers of fs_segment_batch_host (payload, frames, the four result arrays)
-    framesum::SegTables* d_seg_tables = nullptr;
-    SegStage seg_stage[kSegStages];
-    int seg_next = 0;  // the block to wait for when all are busy
-    uint8_t* seg_d_payload = nullptr;
-    uint8_t* seg_d_frames = nullptr;
-    uint8_t* seg_d_arrays = nullptr;
-    uint64_t seg_cap_payload = 0, seg_cap_frames = 0, seg_cap_arrays = 0;
-    // RX coalesce: the kernels' scratch, out / status when the caller passes none, and the device
-    // buffers of fs_coalesce_batch_host (payload; runs, run_of and totals)
-    uint8_t* co_scratch = nullptr;
-    uint8_t* co_results = nullptr;
-    uint8_t* co_d_payload = nullptr;
-    uint8_t* co_d_arrays = nullptr;
-    uint64_t co_cap_scratch = 0, co_cap_results = 0, co_cap_payload = 0, co_cap_arrays = 0;
-    // flow-aware RX coalesce: the kernels' scratch and the device result arrays of
-    // fs_coalesce_flows_batch_host (out / status and the payload share the buffers above). The hash
-    // mask and the steps are all ones / all steps unless the test library's setters change them.
-    uint8_t* fl_scratch = nullptr;
-    uint8_t* fl_d_arrays = nullptr;
-    uint64_t fl_cap_scratch = 0, fl_cap_arrays = 0;
-    uint32_t flow_hash_mask = 0xFFFFFFFFu;
-    uint32_t flow_steps = framesum::kFlowStepsAll;
-    std::string err;
-};
-
-namespace {
+namespace framesum {
+namespace host {
 
 thread_local std::string g_create_err;
 
@@ -132,54 +50,77 @@ fs_status hip_err(fs_ctx* ctx, hipError_t e, const char* what) {
     return set_err(ctx, FS_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-#define FS_HIP(ctx, call)                                   \
-    do {                                                    \
-        hipError_t e_ = (call);                             \
-        if (e_ != hipSuccess) return hip_err(ctx, e_, #call); \
-    } while (0)
-
-// Grow-only staging of one slot; a slot being regrown first waits for its last kernel.
 fs_status ensure_slot(fs_ctx* ctx, HostSlot& sl, uint64_t frame_bytes, uint32_t n) {
-    if (frame_bytes > sl.cap_frames) {
-        if (sl.used) FS_HIP(ctx, hipEventSynchronize(sl.consumed));
-        (void)hipFree(sl.d_frames);
-        sl.d_frames = nullptr;
-        sl.cap_frames = 0;
-        const uint64_t cap = frame_bytes + 256;
-        if (hipMalloc(&sl.d_frames, cap) != hipSuccess) return set_err(ctx, FS_E_NOMEM, "hipMalloc frames staging");
-        sl.cap_frames = cap;
-    }
-    if (n > sl.cap_n) {
-        if (sl.used) FS_HIP(ctx, hipEventSynchronize(sl.consumed));
-        (void)hipFree(sl.d_offsets);
-        (void)hipFree(sl.d_lengths);
-        (void)hipFree(sl.d_out);
-        (void)hipFree(sl.d_status);
-        sl.d_offsets = nullptr;
-        sl.d_lengths = nullptr;
-        sl.d_out = nullptr;
-        sl.d_status = nullptr;
-        sl.cap_n = 0;
-        if (hipMalloc(&sl.d_offsets, (size_t)n * 8) != hipSuccess || hipMalloc(&sl.d_lengths, (size_t)n * 4) != hipSuccess ||
-            hipMalloc(&sl.d_out, (size_t)n * (sizeof(fs_digest) + 1)) != hipSuccess ||
-            hipMalloc(&sl.d_status, (size_t)n) != hipSuccess)
-            return set_err(ctx, FS_E_NOMEM, "hipMalloc descriptor staging");
-        sl.cap_n = n;
-    }
+    const auto grow = [&](DevBuf& b, uint64_t bytes, const char* what) -> fs_status {
+        if (bytes > b.cap && sl.used) FS_HIP(ctx, hipEventSynchronize(sl.consumed));
+        return b.grow(ctx, bytes, what);
+    };
+    const char* const desc = "hipMalloc descriptor staging";
+    fs_status st = grow(sl.frames, frame_bytes, "hipMalloc frames staging");
+    if (st == FS_SUCCESS) st = grow(sl.offsets, (uint64_t)n * 8, desc);
+    if (st == FS_SUCCESS) st = grow(sl.lengths, (uint64_t)n * 4, desc);
+    if (st == FS_SUCCESS) st = grow(sl.out, (uint64_t)n * (sizeof(fs_digest) + 1), desc);
+    if (st == FS_SUCCESS) st = grow(sl.status, n, desc);
+    return st;
+}
+
+fs_status begin_host_call(fs_ctx* ctx) {
+    FS_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->host_dirty) return FS_SUCCESS;
+    FS_HIP(ctx, hipStreamSynchronize(ctx->compute_stream));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+    FS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream2));
+    ctx->host_dirty = false;
     return FS_SUCCESS;
 }
+
+void drain_host_streams(fs_ctx* ctx) {
+    const bool ok = hipStreamSynchronize(ctx->compute_stream) == hipSuccess &&
+                    hipStreamSynchronize(ctx->copy_stream) == hipSuccess &&
+                    hipStreamSynchronize(ctx->copy_stream2) == hipSuccess;
+    if (ok) ctx->host_dirty = false;
+}
+
+hipError_t launch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
+                  uint32_t mtu, fs_digest* out, uint8_t* status, hipStream_t stream, FsOp op, uint8_t* wframes,
+                  uint32_t tx, int force) {
+    const int wgs = ctx->workgroups > 0 && ctx->workgroups < ctx->num_cus ? ctx->workgroups : ctx->num_cus;
+    return launch_digest(frames, offsets, lengths, n, mtu, ctx->d_tables, out, status, stream, wgs, ctx->choice,
+                         ctx->h_report, ctx->d_report, force >= 0 ? force : ctx->force_kernel, op, wframes, tx);
+}
+
+fs_status stage_batch(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, uint64_t lo, uint64_t hi,
+                      const uint64_t* offsets, const uint32_t* lengths, uint32_t n, Staged& s) {
+    uint64_t cpy_lo, cpy_hi;
+    plan::copy_span(lo, hi, frames_bytes, cpy_lo, cpy_hi);
+    HostSlot& sl = ctx->slot[0];
+    const fs_status st = ensure_slot(ctx, sl, cpy_hi - cpy_lo + 64, n);
+    if (st != FS_SUCCESS) return st;
+    ctx->host_dirty = true;  // until this call has waited for all of its work
+    const hipStream_t ks = ctx->compute_stream;
+    if (sl.used) FS_HIP_DRAIN(ctx, hipStreamWaitEvent(ks, sl.consumed, 0));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.frames.p, frames + cpy_lo, cpy_hi - cpy_lo, hipMemcpyHostToDevice, ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.offsets.p, offsets, (size_t)n * 8, hipMemcpyHostToDevice, ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.lengths.p, lengths, (size_t)n * 4, hipMemcpyHostToDevice, ks));
+    s = Staged{&sl, ks, reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(sl.frames.p) - cpy_lo),
+               sl.offsets.as<uint64_t>(), sl.lengths.as<uint32_t>(), sl.out.as<fs_digest>(), sl.status.p};
+    return FS_SUCCESS;
+}
+
+fs_status finish_staged(fs_ctx* ctx, const Staged& s) {
+    FS_HIP_DRAIN(ctx, hipEventRecord(s.sl->consumed, s.ks));
+    s.sl->used = true;
+    FS_HIP_DRAIN(ctx, hipStreamSynchronize(s.ks));
+    ctx->host_dirty = false;
+    return FS_SUCCESS;
+}
+
+}  // namespace host
+}  // namespace framesum
+
+namespace {
 
 // h_pin layout for n frames: offsets (8n) | lengths (4n) | digests (8n) | status (n)
-fs_status ensure_desc(fs_ctx* ctx, uint32_t n) {
-    if (n <= ctx->cap_desc_n) return FS_SUCCESS;
-    (void)hipFree(ctx->d_desc);  // the previous call's kernels have ended (callers synchronize first)
-    ctx->d_desc = nullptr;
-    ctx->cap_desc_n = 0;
-    if (hipMalloc(&ctx->d_desc, (size_t)n * 12 + 64) != hipSuccess) return set_err(ctx, FS_E_NOMEM, "hipMalloc descriptors");
-    ctx->cap_desc_n = n;
-    return FS_SUCCESS;
-}
-
 fs_status ensure_pinned(fs_ctx* ctx, uint32_t n) {
     if (n <= ctx->cap_pin_n) return FS_SUCCESS;
     if (ctx->h_pin) FS_HIP(ctx, hipHostFree(ctx->h_pin));
@@ -196,39 +137,6 @@ fs_status ensure_pinned(fs_ctx* ctx, uint32_t n) {
     ctx->cap_pin_n = n;
     return FS_SUCCESS;
 }
-
-// Every host-staged entry point starts here: the pinned mirrors and the staging slots are free
-// only once the context's compute stream AND both copy streams are idle (a host-staged call that
-// failed half-way may have left odd-chunk copies in flight on copy_stream2 that would otherwise
-// write a slot while the next call stages into it). A call that succeeded left nothing in flight
-// (its results were waited for), so the three synchronizes (~3 us each when idle) run only after
-// a failed call.
-fs_status quiesce_host_streams(fs_ctx* ctx) {
-    if (!ctx->host_dirty) return FS_SUCCESS;
-    FS_HIP(ctx, hipStreamSynchronize(ctx->compute_stream));
-    FS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-    FS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream2));
-    ctx->host_dirty = false;
-    return FS_SUCCESS;
-}
-
-// A host-staged call that fails after it has enqueued work drains the context's streams before it
-// returns (best effort), so that nothing of it still reads the caller's buffers or writes the
-// caller's result arrays (the kernel writes them in place when they are pinned) after the error.
-void drain_host_streams(fs_ctx* ctx) {
-    const bool ok = hipStreamSynchronize(ctx->compute_stream) == hipSuccess &&
-                    hipStreamSynchronize(ctx->copy_stream) == hipSuccess &&
-                    hipStreamSynchronize(ctx->copy_stream2) == hipSuccess;
-    if (ok) ctx->host_dirty = false;
-}
-#define FS_HIP_DRAIN(ctx, call)                  \
-    do {                                         \
-        hipError_t e_ = (call);                  \
-        if (e_ != hipSuccess) {                  \
-            drain_host_streams(ctx);             \
-            return hip_err(ctx, e_, #call);      \
-        }                                        \
-    } while (0)
 
 // Wait on the host for `ev` by polling: HIP's blocking wait wakes the host about 25 us after the
 // work ends, a third of a short host-staged call. After 2 ms of polling (a long
@@ -264,17 +172,6 @@ bool is_pinned(const void* p, size_t bytes) {
     }
     const uintptr_t b = reinterpret_cast<uintptr_t>(start), q = reinterpret_cast<uintptr_t>(p);
     return q >= b && bytes <= size && q - b <= size - bytes;
-}
-
-// One launch of the context's kernel choice.
-// `force` < 0: the context's kernel choice (fs_ctx_set_kernel).
-hipError_t launch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
-                  uint32_t mtu, fs_digest* out, uint8_t* status, hipStream_t stream, framesum::FsOp op,
-                  uint8_t* wframes, uint32_t tx, int force = -1) {
-    const int wgs = ctx->workgroups > 0 && ctx->workgroups < ctx->num_cus ? ctx->workgroups : ctx->num_cus;
-    return framesum::launch_digest(frames, offsets, lengths, n, mtu, ctx->d_tables, out, status, stream, wgs,
-                                   ctx->choice, ctx->h_report, ctx->d_report,
-                                   force >= 0 ? force : ctx->force_kernel, op, wframes, tx);
 }
 
 // The argument checks at the head of a batch entry point `fn` (`aligned`: the kernel reads `frames`
@@ -403,18 +300,12 @@ fs_status fs_ctx_destroy(fs_ctx* ctx) {
     if (ctx->copy_stream2) (void)hipStreamDestroy(ctx->copy_stream2);
     if (ctx->desc_copied) (void)hipEventDestroy(ctx->desc_copied);
     if (ctx->host_done) (void)hipEventDestroy(ctx->host_done);
-    (void)hipFree(ctx->d_desc);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
     if (ctx->compute_stream) (void)hipStreamDestroy(ctx->compute_stream);
     for (HostSlot& sl : ctx->slot) {
         if (sl.copied) (void)hipEventDestroy(sl.copied);
         if (sl.consumed) (void)hipEventDestroy(sl.consumed);
         if (sl.landed) (void)hipEventDestroy(sl.landed);
-        (void)hipFree(sl.d_frames);
-        (void)hipFree(sl.d_offsets);
-        (void)hipFree(sl.d_lengths);
-        (void)hipFree(sl.d_out);
-        (void)hipFree(sl.d_status);
     }
     for (SegStage& sg : ctx->seg_stage) {
         if (sg.done) (void)hipEventSynchronize(sg.done);
@@ -423,56 +314,46 @@ fs_status fs_ctx_destroy(fs_ctx* ctx) {
         (void)hipFree(sg.d);
     }
     (void)hipFree(ctx->d_seg_tables);
-    (void)hipFree(ctx->seg_d_payload);
-    (void)hipFree(ctx->seg_d_frames);
-    (void)hipFree(ctx->seg_d_arrays);
-    (void)hipFree(ctx->co_scratch);
-    (void)hipFree(ctx->co_results);
-    (void)hipFree(ctx->co_d_payload);
-    (void)hipFree(ctx->co_d_arrays);
-    (void)hipFree(ctx->fl_scratch);
-    (void)hipFree(ctx->fl_d_arrays);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->h_report) (void)hipHostFree(const_cast<uint32_t*>(ctx->h_report));
     (void)hipFree(ctx->d_tables);
-    delete ctx;
+    delete ctx;  // (every DevBuf of the context and its slots frees itself here)
     return FS_SUCCESS;
 }
 
 const char* fs_last_error(const fs_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
-fs_status fs_digest_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
-                          uint32_t n, uint32_t mtu, fs_digest* out, uint8_t* status, void* stream) {
+// The three device-resident calls: one launch of `op` on the caller's stream. `wframes`: the frames
+// as the TX fill writes them (null otherwise), `flags` its FS_FILL_* flags (0 otherwise).
+static fs_status digest_resident(fs_ctx* ctx, const char* fn, framesum::FsOp op, const uint8_t* frames, uint8_t* wframes,
+                                 uint32_t flags, const uint64_t* offsets, const uint32_t* lengths, uint32_t n, uint32_t mtu,
+                                 fs_digest* out, uint8_t* status, void* stream) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    const fs_status st = check_batch(ctx, "fs_digest_batch", frames, offsets, lengths, n, out, true);
+    if (flags & ~(uint32_t)(FS_FILL_CSUM | FS_FCS_APPEND)) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": unknown flags");
+    const fs_status st = check_batch(ctx, fn, frames, offsets, lengths, n, out, true);
     if (n == 0 || st != FS_SUCCESS) return st;
     FS_HIP(ctx, hipSetDevice(ctx->device));
-    FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, reinterpret_cast<hipStream_t>(stream), framesum::FsOp::kDigest, nullptr, 0));
+    FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, reinterpret_cast<hipStream_t>(stream), op, wframes, flags));
     return FS_SUCCESS;
+}
+
+fs_status fs_digest_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                          uint32_t n, uint32_t mtu, fs_digest* out, uint8_t* status, void* stream) {
+    return digest_resident(ctx, "fs_digest_batch", framesum::FsOp::kDigest, frames, nullptr, 0, offsets, lengths, n, mtu, out,
+                           status, stream);
 }
 
 fs_status fs_fill_batch(fs_ctx* ctx, uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
                         uint32_t mtu, uint32_t flags, fs_digest* out, uint8_t* status, void* stream) {
-    if (!ctx) return FS_E_INVALID;
-    ctx->err.clear();
-    if (flags & ~(uint32_t)(FS_FILL_CSUM | FS_FCS_APPEND)) return set_err(ctx, FS_E_INVALID, "fs_fill_batch: unknown flags");
-    const fs_status st = check_batch(ctx, "fs_fill_batch", frames, offsets, lengths, n, out, true);
-    if (n == 0 || st != FS_SUCCESS) return st;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, reinterpret_cast<hipStream_t>(stream), framesum::FsOp::kFill, frames, flags));
-    return FS_SUCCESS;
+    return digest_resident(ctx, "fs_fill_batch", framesum::FsOp::kFill, frames, frames, flags, offsets, lengths, n, mtu, out,
+                           status, stream);
 }
 
 fs_status fs_digest_batch_fcs(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
                               uint32_t n, uint32_t mtu, fs_digest* out, uint8_t* status, void* stream) {
-    if (!ctx) return FS_E_INVALID;
-    ctx->err.clear();
-    const fs_status st = check_batch(ctx, "fs_digest_batch_fcs", frames, offsets, lengths, n, out, true);
-    if (n == 0 || st != FS_SUCCESS) return st;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, reinterpret_cast<hipStream_t>(stream), framesum::FsOp::kFcs, nullptr, 0));
-    return FS_SUCCESS;
+    return digest_resident(ctx, "fs_digest_batch_fcs", framesum::FsOp::kFcs, frames, nullptr, 0, offsets, lengths, n, mtu, out,
+                           status, stream);
 }
 
 // The descriptor scan of a host-staged call, compiled for AVX-512 and AVX2 beside the baseline
@@ -521,14 +402,14 @@ static fs_status host_single(fs_ctx* ctx, const uint8_t* frames, uint64_t frames
     const hipStream_t ks = ctx->compute_stream;
     // the frames behind the descriptors (issued by the caller before the scan), then the kernel, in
     // the compute stream's order: no cross-stream event between them
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_frames, frames + cpy_lo, cpy_hi - cpy_lo, hipMemcpyHostToDevice, ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.frames.p, frames + cpy_lo, cpy_hi - cpy_lo, hipMemcpyHostToDevice, ks));
     if (ctx->fault_chunk == 0) {
         drain_host_streams(ctx);
         return set_err(ctx, FS_E_NOMEM, "fs_digest_batch_host: injected failure (test hook)");
     }
-    const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(sl.d_frames) - cpy_lo);
-    const uint64_t* d_off = reinterpret_cast<const uint64_t*>(ctx->d_desc);
-    const uint32_t* d_len = reinterpret_cast<const uint32_t*>(ctx->d_desc + (size_t)n * 8);
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(sl.frames.p) - cpy_lo);
+    const uint64_t* d_off = ctx->desc.as<const uint64_t>();
+    const uint32_t* d_len = ctx->desc.as<const uint32_t>((size_t)n * 8);
     FS_HIP_DRAIN(ctx, launch(ctx, base, d_off, d_len, n, mtu, rt.d_out, rt.d_st, ks, framesum::FsOp::kDigest, nullptr, 0,
                              force));
     FS_HIP_DRAIN(ctx, hipEventRecord(sl.consumed, ks));
@@ -567,8 +448,7 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
     ctx->err.clear();
     const fs_status ast = check_batch(ctx, "fs_digest_batch_host", frames, offsets, lengths, n, out, false);
     if (n == 0 || ast != FS_SUCCESS) return ast;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    fs_status pst = quiesce_host_streams(ctx);
+    fs_status pst = begin_host_call(ctx);
     if (pst != FS_SUCCESS) return pst;
     if (n <= kChunkFrames && ctx->force_kernel != 2 && ctx->force_kernel != 3 && ctx->force_kernel != 4) {
         // A batch of short frames whose frames, offsets and lengths are all in pinned host memory:
@@ -594,7 +474,7 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
         // any frame byte is copied): straight from the caller's arrays when they are pinned (one
         // copy when the lengths follow the offsets, as the Go binding stages them), else through
         // the pinned mirror.
-        pst = ensure_desc(ctx, n);
+        pst = ctx->desc.grow(ctx, (uint64_t)n * 12, "hipMalloc descriptors");
         if (pst == FS_SUCCESS) pst = ensure_pinned(ctx, n);
         if (pst != FS_SUCCESS) return pst;
         ctx->host_dirty = true;  // until this call has waited for all of its work
@@ -609,10 +489,10 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
         }
         const hipStream_t ks = ctx->compute_stream;
         if (reinterpret_cast<const uint8_t*>(src_off) + (size_t)n * 8 == reinterpret_cast<const uint8_t*>(src_len)) {
-            FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->d_desc, src_off, (size_t)n * 12, hipMemcpyHostToDevice, ks));
+            FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->desc.p, src_off, (size_t)n * 12, hipMemcpyHostToDevice, ks));
         } else {
-            FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->d_desc, src_off, (size_t)n * 8, hipMemcpyHostToDevice, ks));
-            FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->d_desc + (size_t)n * 8, src_len, (size_t)n * 4, hipMemcpyHostToDevice, ks));
+            FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->desc.p, src_off, (size_t)n * 8, hipMemcpyHostToDevice, ks));
+            FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->desc.p + (size_t)n * 8, src_len, (size_t)n * 4, hipMemcpyHostToDevice, ks));
         }
         const framesum::plan::Scan sc = scan_host(ctx, offsets, lengths, n, frames_bytes);
         if (sc.bad < n) {
@@ -631,7 +511,7 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
     ctx->last_host_path = 3;
     pst = ensure_pinned(ctx, n);
     if (pst != FS_SUCCESS) return pst;
-    pst = ensure_desc(ctx, n);
+    pst = ctx->desc.grow(ctx, (uint64_t)n * 12, "hipMalloc descriptors");
     if (pst != FS_SUCCESS) return pst;
     uint64_t* h_off = reinterpret_cast<uint64_t*>(ctx->h_pin);
     uint32_t* h_len = reinterpret_cast<uint32_t*>(ctx->h_pin + (size_t)n * 8);
@@ -653,7 +533,7 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
         if (st != FS_SUCCESS) return st;
         const hipStream_t cs = (k & 1u) ? ctx->copy_stream2 : ctx->copy_stream;
         if (sl.used) FS_HIP(ctx, hipStreamWaitEvent(cs, sl.consumed, 0));  // chunk k - kHostSlots done with it
-        FS_HIP(ctx, hipMemcpyAsync(sl.d_frames, frames + c.cpy_lo, c.cpy_hi - c.cpy_lo, hipMemcpyHostToDevice, cs));
+        FS_HIP(ctx, hipMemcpyAsync(sl.frames.p, frames + c.cpy_lo, c.cpy_hi - c.cpy_lo, hipMemcpyHostToDevice, cs));
         FS_HIP(ctx, hipEventRecord(sl.copied, cs));
         return FS_SUCCESS;
     };
@@ -671,9 +551,9 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
     if (st != FS_SUCCESS) return st;
     std::memcpy(h_off, offsets, (size_t)n * 8);
     std::memcpy(h_len, lengths, (size_t)n * 4);
-    const uint64_t* d_off = reinterpret_cast<const uint64_t*>(ctx->d_desc);
-    const uint32_t* d_len = reinterpret_cast<const uint32_t*>(ctx->d_desc + (size_t)n * 8);
-    FS_HIP(ctx, hipMemcpyAsync(ctx->d_desc, h_off, (size_t)n * 12, hipMemcpyHostToDevice, ctx->copy_stream2));
+    const uint64_t* d_off = ctx->desc.as<const uint64_t>();
+    const uint32_t* d_len = ctx->desc.as<const uint32_t>((size_t)n * 8);
+    FS_HIP(ctx, hipMemcpyAsync(ctx->desc.p, h_off, (size_t)n * 12, hipMemcpyHostToDevice, ctx->copy_stream2));
     FS_HIP(ctx, hipEventRecord(ctx->desc_copied, ctx->copy_stream2));
     FS_HIP(ctx, hipStreamWaitEvent(ks, ctx->desc_copied, 0));
     for (size_t chunk = 0; chunk < chunks.size(); ++chunk) {
@@ -689,13 +569,13 @@ fs_status fs_digest_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fram
             return set_err(ctx, FS_E_NOMEM, "fs_digest_batch_host: injected failure (test hook)");
         FS_HIP(ctx, hipStreamWaitEvent(ks, sl.copied, 0));
         // the kernel addresses frame i at base + offsets[i]: base = staging - cpy_lo (4-B aligned)
-        const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(sl.d_frames) - cpy_lo);
-        FS_HIP(ctx, launch(ctx, base, d_off + c0, d_len + c0, cnt, mtu, sl.d_out, status ? sl.d_status : nullptr, ks,
+        const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(sl.frames.p) - cpy_lo);
+        FS_HIP(ctx, launch(ctx, base, d_off + c0, d_len + c0, cnt, mtu, sl.out.as<fs_digest>(), status ? sl.status.p : nullptr, ks,
                            framesum::FsOp::kDigest, nullptr, 0, force));
         FS_HIP(ctx, hipEventRecord(sl.consumed, ks));
         sl.used = true;
-        FS_HIP(ctx, hipMemcpyAsync(h_out + c0, sl.d_out, (size_t)cnt * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
-        if (status) FS_HIP(ctx, hipMemcpyAsync(h_st + c0, sl.d_status, cnt, hipMemcpyDeviceToHost, ks));
+        FS_HIP(ctx, hipMemcpyAsync(h_out + c0, sl.out.p, (size_t)cnt * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
+        if (status) FS_HIP(ctx, hipMemcpyAsync(h_st + c0, sl.status.p, cnt, hipMemcpyDeviceToHost, ks));
         FS_HIP(ctx, hipEventRecord(sl.landed, ks));
         // chunk - 2's results while this one streams (its slot's `landed` is re-recorded by chunk + 1)
         if (chunk >= 2) {
@@ -724,524 +604,31 @@ fs_status fs_fill_batch_host(fs_ctx* ctx, uint8_t* frames, uint64_t frames_bytes
     // One staged span [lo, hi) (the frames and, with FS_FCS_APPEND, their FCS bytes), copied in,
     // filled, copied back. Not chunk-pipelined: written spans of unordered batches may interleave.
     const uint32_t extra = (flags & FS_FCS_APPEND) ? 4u : 0u;
-    const uint32_t bad = framesum::plan::first_frame_out_of_range(offsets, lengths, n, frames_bytes, extra);
-    if (bad < n)
-        return set_err(ctx, FS_E_INVALID, "fs_fill_batch_host: frame " + std::to_string(bad) + " ends past frames_bytes");
-    uint64_t lo = UINT64_MAX, hi = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t o = offsets[i], e = o + lengths[i] + extra;
-        lo = o < lo ? o : lo;
-        hi = e > hi ? e : hi;
-    }
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    fs_status pst = quiesce_host_streams(ctx);
-    if (pst != FS_SUCCESS) return pst;
-    ctx->host_dirty = true;  // until this call has waited for all of its work
-    pst = ensure_pinned(ctx, n);
-    if (pst != FS_SUCCESS) return pst;
+    const framesum::plan::Scan sc = framesum::plan::scan_batch(offsets, lengths, n, frames_bytes, extra);
+    if (sc.bad < n)
+        return set_err(ctx, FS_E_INVALID, "fs_fill_batch_host: frame " + std::to_string(sc.bad) + " ends past frames_bytes");
+    const uint64_t lo = sc.lo, hi = sc.hi + extra;
+    fs_status st = begin_host_call(ctx);
+    if (st == FS_SUCCESS) st = ensure_pinned(ctx, n);
+    if (st != FS_SUCCESS) return st;
     uint64_t* h_off = reinterpret_cast<uint64_t*>(ctx->h_pin);
     uint32_t* h_len = reinterpret_cast<uint32_t*>(ctx->h_pin + (size_t)n * 8);
     fs_digest* h_out = reinterpret_cast<fs_digest*>(ctx->h_pin + (size_t)n * 12);
     uint8_t* h_st = ctx->h_pin + (size_t)n * 20;
     std::memcpy(h_off, offsets, (size_t)n * 8);
     std::memcpy(h_len, lengths, (size_t)n * 4);
-    uint64_t cpy_lo, cpy_hi;
-    framesum::plan::copy_span(lo, hi, frames_bytes, cpy_lo, cpy_hi);
-    HostSlot& sl = ctx->slot[0];
-    fs_status st = ensure_slot(ctx, sl, cpy_hi - cpy_lo + 64, n);
+    Staged s;
+    st = stage_batch(ctx, frames, frames_bytes, lo, hi, h_off, h_len, n, s);
     if (st != FS_SUCCESS) return st;
-    hipStream_t ks = ctx->compute_stream;
-    if (sl.used) FS_HIP(ctx, hipStreamWaitEvent(ks, sl.consumed, 0));
-    FS_HIP(ctx, hipMemcpyAsync(sl.d_frames, frames + cpy_lo, cpy_hi - cpy_lo, hipMemcpyHostToDevice, ks));
-    FS_HIP(ctx, hipMemcpyAsync(sl.d_offsets, h_off, (size_t)n * 8, hipMemcpyHostToDevice, ks));
-    FS_HIP(ctx, hipMemcpyAsync(sl.d_lengths, h_len, (size_t)n * 4, hipMemcpyHostToDevice, ks));
-    uint8_t* base = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(sl.d_frames) - cpy_lo);
-    FS_HIP(ctx, launch(ctx, base, sl.d_offsets, sl.d_lengths, n, mtu, sl.d_out, status ? sl.d_status : nullptr, ks,
-                       framesum::FsOp::kFill, base, flags));
-    FS_HIP(ctx, hipMemcpyAsync(frames + lo, sl.d_frames + (lo - cpy_lo), hi - lo, hipMemcpyDeviceToHost, ks));
-    FS_HIP(ctx, hipMemcpyAsync(h_out, sl.d_out, (size_t)n * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
-    if (status) FS_HIP(ctx, hipMemcpyAsync(h_st, sl.d_status, n, hipMemcpyDeviceToHost, ks));
-    FS_HIP(ctx, hipEventRecord(sl.consumed, ks));
-    sl.used = true;
-    FS_HIP(ctx, hipStreamSynchronize(ks));
-    ctx->host_dirty = false;
+    FS_HIP_DRAIN(ctx, launch(ctx, s.base, s.d_off, s.d_len, n, mtu, s.d_out, status ? s.d_st : nullptr, s.ks,
+                             framesum::FsOp::kFill, s.base, flags));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(frames + lo, s.base + lo, hi - lo, hipMemcpyDeviceToHost, s.ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(h_out, s.d_out, (size_t)n * sizeof(fs_digest), hipMemcpyDeviceToHost, s.ks));
+    if (status) FS_HIP_DRAIN(ctx, hipMemcpyAsync(h_st, s.d_st, n, hipMemcpyDeviceToHost, s.ks));
+    st = finish_staged(ctx, s);
+    if (st != FS_SUCCESS) return st;
     std::memcpy(out, h_out, (size_t)n * sizeof(fs_digest));
     if (status) std::memcpy(status, h_st, n);
-    return FS_SUCCESS;
-}
-
-// ---- TX frame build (fs_segment_layout / fs_segment_batch / fs_segment_batch_host) ----
-
-// Every check of a segment call that needs no device: flags, align, each send, the totals.
-static fs_status segment_check(fs_ctx* ctx, const char* fn, const fs_tx_send* sends, uint32_t n_sends, uint32_t flags,
-                               uint32_t align, bool have_payload, uint64_t payload_bytes, framesum::segment::Layout& L) {
-    namespace seg = framesum::segment;
-    if (!seg::valid_flags(flags)) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": flags must be 0 or FS_FCS_APPEND");
-    if (!seg::valid_align(align))
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": align must be a power of two from 1 to 4096");
-    if (!sends) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");
-    L = seg::layout(sends, n_sends, flags, align, have_payload, payload_bytes);
-    if (L.bad != seg::kGood)
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": send " + std::to_string(L.bad_send) + ": " + seg::bad_text(L.bad));
-    return FS_SUCCESS;
-}
-
-// A staging block of at least `bytes` bytes whose previous kernel has ended.
-static fs_status segment_stage_block(fs_ctx* ctx, uint64_t bytes, SegStage** out) {
-    SegStage* pick = nullptr;
-    for (SegStage& sg : ctx->seg_stage) {
-        if (sg.used) {
-            const hipError_t q = hipEventQuery(sg.done);
-            if (q == hipErrorNotReady) continue;
-            if (q != hipSuccess) return hip_err(ctx, q, "hipEventQuery of a staging block");
-            sg.used = false;
-        }
-        if (!pick || (pick->cap < bytes && sg.cap >= bytes)) pick = &sg;
-        if (pick->cap >= bytes) break;
-    }
-    if (!pick) {  // every block is in flight: wait for the oldest
-        pick = &ctx->seg_stage[ctx->seg_next];
-        ctx->seg_next = (ctx->seg_next + 1) % kSegStages;
-        FS_HIP(ctx, hipEventSynchronize(pick->done));
-        pick->used = false;
-    }
-    if (!pick->done) FS_HIP(ctx, hipEventCreateWithFlags(&pick->done, hipEventDisableTiming));
-    if (pick->cap < bytes) {
-        if (pick->h) (void)hipHostFree(pick->h);
-        (void)hipFree(pick->d);
-        pick->h = nullptr;
-        pick->d = nullptr;
-        pick->cap = 0;
-        const uint64_t cap = (bytes + 4095) & ~4095ull;
-        if (hipHostMalloc(reinterpret_cast<void**>(&pick->h), cap, hipHostMallocDefault) != hipSuccess ||
-            hipMalloc(&pick->d, cap) != hipSuccess)
-            return set_err(ctx, FS_E_NOMEM, "fs_segment_batch: staging allocation failed");
-        pick->cap = cap;
-    }
-    *out = pick;
-    return FS_SUCCESS;
-}
-
-// Stage a checked batch and enqueue its copy and its one kernel on `stream`.
-static fs_status segment_enqueue(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_sends,
-                                 const framesum::segment::Layout& L, const uint8_t* payload, uint32_t mtu, uint32_t flags,
-                                 uint32_t align, uint8_t* frames, uint64_t* offsets, uint32_t* lengths, fs_digest* out,
-                                 uint8_t* status, hipStream_t stream) {
-    namespace seg = framesum::segment;
-    if (!ctx->d_seg_tables) {
-        framesum::SegTables* h = new (std::nothrow) framesum::SegTables;
-        if (!h) return set_err(ctx, FS_E_NOMEM, "fs_segment_batch: out of host memory");
-        framesum::build_segment_tables(h);
-        hipError_t e = hipMalloc(&ctx->d_seg_tables, sizeof(framesum::SegTables));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_seg_tables, h, sizeof(framesum::SegTables), hipMemcpyHostToDevice);
-        delete h;
-        if (e != hipSuccess) {
-            (void)hipFree(ctx->d_seg_tables);
-            ctx->d_seg_tables = nullptr;
-            return hip_err(ctx, e, "fs_segment_batch: table upload");
-        }
-    }
-    const seg::Block b = seg::block_of(n_sends, L.id_entries);
-    SegStage* sg = nullptr;
-    const fs_status st = segment_stage_block(ctx, b.bytes, &sg);
-    if (st != FS_SUCCESS) return st;
-    seg::stage(sends, n_sends, flags, align, b, sg->h);
-    FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, b.bytes, hipMemcpyHostToDevice, stream));
-    // two workgroups per CU (their tables fit its LDS twice) unless fs_ctx_set_workgroups caps the grid
-    const int wgs = ctx->workgroups > 0 && ctx->workgroups < 2 * ctx->num_cus ? ctx->workgroups : 2 * ctx->num_cus;
-    sg->used = true;  // (from here on the block may be read by queued work)
-    const hipError_t le = framesum::launch_segment(sg->d, b, n_sends, (uint32_t)L.n_frames, payload, frames, offsets, lengths,
-                                                   out, status, mtu, flags, align, ctx->d_seg_tables, wgs, stream);
-    const hipError_t re = hipEventRecord(sg->done, stream);
-    if (le != hipSuccess) return hip_err(ctx, le, "fs_segment_batch: launch");
-    if (re != hipSuccess) return hip_err(ctx, re, "hipEventRecord(sg->done, stream)");
-    return FS_SUCCESS;
-}
-
-fs_status fs_segment_layout(const fs_tx_send* sends, uint32_t n_sends, uint32_t flags, uint32_t align, uint64_t* n_frames,
-                            uint64_t* frames_bytes) {
-    g_create_err.clear();
-    framesum::segment::Layout L;
-    if (n_sends == 0) {
-        if (!framesum::segment::valid_flags(flags) || !framesum::segment::valid_align(align))
-            return set_err(nullptr, FS_E_INVALID, "fs_segment_layout: bad flags or align");
-    } else {
-        const fs_status st = segment_check(nullptr, "fs_segment_layout", sends, n_sends, flags, align, false, 0, L);
-        if (st != FS_SUCCESS) return st;
-    }
-    if (n_frames) *n_frames = L.n_frames;
-    if (frames_bytes) *frames_bytes = L.frames_bytes;
-    return FS_SUCCESS;
-}
-
-// The checks fs_segment_batch and fs_segment_batch_host share, all before any device call.
-static fs_status segment_args(fs_ctx* ctx, const char* fn, const fs_tx_send* sends, uint32_t n_sends, const uint8_t* payload,
-                              uint64_t payload_bytes, uint32_t flags, uint32_t align, const uint8_t* frames,
-                              uint64_t frames_bytes, framesum::segment::Layout& L) {
-    const fs_status st = segment_check(ctx, fn, sends, n_sends, flags, align, true, payload_bytes, L);
-    if (st != FS_SUCCESS) return st;
-    if (!frames) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");
-    if (!payload && L.payload > 0)
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null payload");
-    if (frames_bytes < L.frames_bytes)
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": frames_bytes " + std::to_string(frames_bytes) +
-                                              " is below the layout's " + std::to_string(L.frames_bytes));
-    return FS_SUCCESS;
-}
-
-fs_status fs_segment_batch(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_sends, const uint8_t* payload,
-                           uint64_t payload_bytes, uint32_t mtu, uint32_t flags, uint32_t align, uint8_t* frames,
-                           uint64_t frames_bytes, uint64_t* offsets, uint32_t* lengths, fs_digest* out, uint8_t* status,
-                           void* stream) {
-    if (!ctx) return FS_E_INVALID;
-    ctx->err.clear();
-    if (n_sends == 0) return FS_SUCCESS;
-    framesum::segment::Layout L;
-    const fs_status st = segment_args(ctx, "fs_segment_batch", sends, n_sends, payload, payload_bytes, flags, align, frames,
-                                      frames_bytes, L);
-    if (st != FS_SUCCESS) return st;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    return segment_enqueue(ctx, sends, n_sends, L, payload, mtu, flags, align, frames, offsets, lengths, out, status,
-                           reinterpret_cast<hipStream_t>(stream));
-}
-
-static fs_status segment_grow(fs_ctx* ctx, uint8_t** p, uint64_t* cap, uint64_t bytes) {
-    if (bytes <= *cap) return FS_SUCCESS;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, bytes + 256) != hipSuccess) return set_err(ctx, FS_E_NOMEM, "hipMalloc of a staging buffer");
-    *cap = bytes + 256;
-    return FS_SUCCESS;
-}
-
-fs_status fs_segment_batch_host(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_sends, const uint8_t* payload,
-                                uint64_t payload_bytes, uint32_t mtu, uint32_t flags, uint32_t align, uint8_t* frames,
-                                uint64_t frames_bytes, uint64_t* offsets, uint32_t* lengths, fs_digest* out,
-                                uint8_t* status) {
-    if (!ctx) return FS_E_INVALID;
-    ctx->err.clear();
-    if (n_sends == 0) return FS_SUCCESS;
-    framesum::segment::Layout L;
-    const fs_status ast = segment_args(ctx, "fs_segment_batch_host", sends, n_sends, payload, payload_bytes, flags, align,
-                                       frames, frames_bytes, L);
-    if (ast != FS_SUCCESS) return ast;
-    // the payload bytes the sends use
-    uint64_t lo = UINT64_MAX, hi = 0;
-    for (uint32_t i = 0; i < n_sends; ++i) {
-        if (sends[i].payload_len == 0) continue;
-        const uint64_t o = sends[i].payload_off, e = o + sends[i].payload_len;
-        lo = o < lo ? o : lo;
-        hi = e > hi ? e : hi;
-    }
-    if (hi <= lo) lo = hi = 0;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    fs_status st = quiesce_host_streams(ctx);
-    if (st != FS_SUCCESS) return st;
-    const uint64_t n = L.n_frames;
-    st = segment_grow(ctx, &ctx->seg_d_payload, &ctx->seg_cap_payload, hi - lo);
-    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->seg_d_frames, &ctx->seg_cap_frames, L.frames_bytes);
-    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->seg_d_arrays, &ctx->seg_cap_arrays, n * 21);
-    if (st != FS_SUCCESS) return st;
-    ctx->host_dirty = true;  // until this call has waited for all of its work
-    const hipStream_t ks = ctx->compute_stream;
-    // pinned memory (fs_host_alloc) is copied from and to directly; pageable memory goes through the
-    // runtime's own pinned staging
-    if (hi > lo) FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->seg_d_payload, payload + lo, hi - lo, hipMemcpyHostToDevice, ks));
-    // the kernel writes frame and FCS bytes only: when the slots leave gaps (align > 1), the span
-    // goes in first so that the copy back returns the caller's own bytes there
-    if (L.written != L.frames_bytes)
-        FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->seg_d_frames, frames, L.frames_bytes, hipMemcpyHostToDevice, ks));
-    uint64_t* d_off = reinterpret_cast<uint64_t*>(ctx->seg_d_arrays);
-    fs_digest* d_out = reinterpret_cast<fs_digest*>(ctx->seg_d_arrays + n * 8);
-    uint32_t* d_len = reinterpret_cast<uint32_t*>(ctx->seg_d_arrays + n * 16);
-    uint8_t* d_st = ctx->seg_d_arrays + n * 20;
-    const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(ctx->seg_d_payload) - lo);
-    st = segment_enqueue(ctx, sends, n_sends, L, base, mtu, flags, align, ctx->seg_d_frames, offsets ? d_off : nullptr,
-                         lengths ? d_len : nullptr, out ? d_out : nullptr, status ? d_st : nullptr, ks);
-    if (st != FS_SUCCESS) {
-        drain_host_streams(ctx);
-        return st;
-    }
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(frames, ctx->seg_d_frames, L.frames_bytes, hipMemcpyDeviceToHost, ks));
-    if (offsets) FS_HIP_DRAIN(ctx, hipMemcpyAsync(offsets, d_off, n * 8, hipMemcpyDeviceToHost, ks));
-    if (lengths) FS_HIP_DRAIN(ctx, hipMemcpyAsync(lengths, d_len, n * 4, hipMemcpyDeviceToHost, ks));
-    if (out) FS_HIP_DRAIN(ctx, hipMemcpyAsync(out, d_out, n * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
-    if (status) FS_HIP_DRAIN(ctx, hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ks));
-    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
-    ctx->host_dirty = false;
-    return FS_SUCCESS;
-}
-
-// ---- RX coalesce (fs_coalesce_batch / fs_coalesce_batch_host) ----
-
-// Every check of a coalesce call, none of which needs a device. An empty batch needs only `totals`.
-static fs_status coalesce_check(fs_ctx* ctx, const char* fn, const void* frames, const void* offsets, const void* lengths,
-                                uint32_t n, uint32_t flags, const void* payload, uint64_t payload_cap, const void* runs,
-                                const void* totals, bool aligned) {
-    if (flags & ~(uint32_t)FS_RX_FCS) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": flags must be 0 or FS_RX_FCS");
-    if (n > kMaxFrames) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": n too large (at most 2^31 frames per call)");
-    if (!totals) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");
-    if (n == 0) return FS_SUCCESS;
-    if (!frames || !offsets || !lengths || !runs) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");
-    if (!payload && payload_cap != 0) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null payload with a non-zero payload_cap");
-    if (aligned && (reinterpret_cast<uintptr_t>(frames) & 3u))
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": frames must be 4-byte aligned");
-    return FS_SUCCESS;
-}
-
-// The digest launch and the coalesce launches of a checked, non-empty device-resident batch on `stream`.
-static fs_status coalesce_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
-                                  uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
-                                  fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals, fs_digest* out, uint8_t* status,
-                                  hipStream_t stream) {
-    fs_status st = segment_grow(ctx, &ctx->co_scratch, &ctx->co_cap_scratch, framesum::coalesce_scratch(n).bytes);
-    if (st == FS_SUCCESS && (!out || !status)) st = segment_grow(ctx, &ctx->co_results, &ctx->co_cap_results, (uint64_t)n * 9);
-    if (st != FS_SUCCESS) return st;
-    if (!out) out = reinterpret_cast<fs_digest*>(ctx->co_results);
-    if (!status) status = ctx->co_results + (uint64_t)n * 8;
-    FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, stream,
-                       (flags & FS_RX_FCS) ? framesum::FsOp::kFcs : framesum::FsOp::kDigest, nullptr, 0));
-    // up to 8 workgroups of 256 lanes per CU unless fs_ctx_set_workgroups caps the grids
-    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
-    FS_HIP(ctx, framesum::launch_coalesce(frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, run_of,
-                                          totals, ctx->co_scratch, wgs, stream));
-    return FS_SUCCESS;
-}
-
-fs_status fs_coalesce_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
-                            uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
-                            fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals, fs_digest* out, uint8_t* status,
-                            void* stream) {
-    if (!ctx) return FS_E_INVALID;
-    ctx->err.clear();
-    const fs_status st = coalesce_check(ctx, "fs_coalesce_batch", frames, offsets, lengths, n, flags, payload, payload_cap,
-                                        runs, totals, true);
-    if (st != FS_SUCCESS) return st;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    if (n == 0) {
-        FS_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(fs_rx_totals), reinterpret_cast<hipStream_t>(stream)));
-        return FS_SUCCESS;
-    }
-    return coalesce_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, payload, payload_cap, runs, run_of, totals, out,
-                            status, reinterpret_cast<hipStream_t>(stream));
-}
-
-fs_status fs_coalesce_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
-                                 const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload,
-                                 uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals,
-                                 fs_digest* out, uint8_t* status) {
-    if (!ctx) return FS_E_INVALID;
-    ctx->err.clear();
-    const fs_status ast = coalesce_check(ctx, "fs_coalesce_batch_host", frames, offsets, lengths, n, flags, payload,
-                                         payload_cap, runs, totals, false);
-    if (ast != FS_SUCCESS) return ast;
-    if (n == 0) {
-        std::memset(totals, 0, sizeof(fs_rx_totals));
-        return FS_SUCCESS;
-    }
-    const uint32_t bad = framesum::plan::first_frame_out_of_range(offsets, lengths, n, frames_bytes);
-    if (bad < n)
-        return set_err(ctx, FS_E_INVALID, "fs_coalesce_batch_host: frame " + std::to_string(bad) + " ends past frames_bytes");
-    // the staged span [lo, hi), and the most payload the batch can hold
-    uint64_t lo = UINT64_MAX, hi = 0, most = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t o = offsets[i], e = o + lengths[i];
-        lo = o < lo ? o : lo;
-        hi = e > hi ? e : hi;
-        most += lengths[i];
-    }
-    const uint64_t d_cap = payload_cap < most ? payload_cap : most;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    fs_status st = quiesce_host_streams(ctx);
-    if (st != FS_SUCCESS) return st;
-    uint64_t cpy_lo, cpy_hi;
-    framesum::plan::copy_span(lo, hi, frames_bytes, cpy_lo, cpy_hi);
-    HostSlot& sl = ctx->slot[0];
-    st = ensure_slot(ctx, sl, cpy_hi - cpy_lo + 64, n);
-    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->co_d_payload, &ctx->co_cap_payload, d_cap);
-    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->co_d_arrays, &ctx->co_cap_arrays, (uint64_t)n * 28 + 16);
-    if (st != FS_SUCCESS) return st;
-    ctx->host_dirty = true;  // until this call has waited for all of its work
-    const hipStream_t ks = ctx->compute_stream;
-    fs_rx_totals* d_totals = reinterpret_cast<fs_rx_totals*>(ctx->co_d_arrays);
-    fs_rx_run* d_runs = reinterpret_cast<fs_rx_run*>(ctx->co_d_arrays + 16);
-    uint32_t* d_run_of = reinterpret_cast<uint32_t*>(ctx->co_d_arrays + 16 + (uint64_t)n * 24);
-    if (sl.used) FS_HIP_DRAIN(ctx, hipStreamWaitEvent(ks, sl.consumed, 0));
-    // pinned memory (fs_host_alloc) is copied from and to directly; pageable memory goes through the
-    // runtime's own pinned staging
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_frames, frames + cpy_lo, cpy_hi - cpy_lo, hipMemcpyHostToDevice, ks));
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_offsets, offsets, (size_t)n * 8, hipMemcpyHostToDevice, ks));
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_lengths, lengths, (size_t)n * 4, hipMemcpyHostToDevice, ks));
-    const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(sl.d_frames) - cpy_lo);
-    st = coalesce_enqueue(ctx, base, sl.d_offsets, sl.d_lengths, n, mtu, flags, ctx->co_d_payload, d_cap, d_runs,
-                          run_of ? d_run_of : nullptr, d_totals, sl.d_out, sl.d_status, ks);
-    if (st != FS_SUCCESS) {
-        drain_host_streams(ctx);
-        return st;
-    }
-    // the totals and how far the payload got written decide what else comes back
-    fs_rx_totals t;
-    uint64_t copied = 0;
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&t, d_totals, sizeof t, hipMemcpyDeviceToHost, ks));
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&copied, ctx->co_scratch + framesum::coalesce_scratch(n).copied, 8,
-                                     hipMemcpyDeviceToHost, ks));
-    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
-    if (copied > d_cap || t.n_runs > n) {
-        drain_host_streams(ctx);
-        return set_err(ctx, FS_E_HIP, "fs_coalesce_batch_host: inconsistent totals from the device");
-    }
-    if (copied) FS_HIP_DRAIN(ctx, hipMemcpyAsync(payload, ctx->co_d_payload, copied, hipMemcpyDeviceToHost, ks));
-    if (t.n_runs) FS_HIP_DRAIN(ctx, hipMemcpyAsync(runs, d_runs, (size_t)t.n_runs * sizeof(fs_rx_run), hipMemcpyDeviceToHost, ks));
-    if (run_of) FS_HIP_DRAIN(ctx, hipMemcpyAsync(run_of, d_run_of, (size_t)n * 4, hipMemcpyDeviceToHost, ks));
-    if (out) FS_HIP_DRAIN(ctx, hipMemcpyAsync(out, sl.d_out, (size_t)n * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
-    if (status) FS_HIP_DRAIN(ctx, hipMemcpyAsync(status, sl.d_status, n, hipMemcpyDeviceToHost, ks));
-    FS_HIP_DRAIN(ctx, hipEventRecord(sl.consumed, ks));
-    sl.used = true;
-    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
-    ctx->host_dirty = false;
-    *totals = t;
-    return FS_SUCCESS;
-}
-
-// ---- Flow-aware RX coalesce (fs_coalesce_flows_batch / fs_coalesce_flows_batch_host) ----
-
-static fs_status flows_check(fs_ctx* ctx, const char* fn, const void* frames, const void* offsets, const void* lengths,
-                             uint32_t n, uint32_t flags, const void* payload, uint64_t payload_cap, const void* runs,
-                             const void* order, const void* totals, bool aligned) {
-    if (n > framesum::flows::kMaxFrames)
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": n too large (at most 2^30 frames per call)");
-    const fs_status st =
-        coalesce_check(ctx, fn, frames, offsets, lengths, n, flags, payload, payload_cap, runs, totals, aligned);
-    if (st != FS_SUCCESS) return st;
-    if (n != 0 && !order) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");  // (as `runs`)
-    return FS_SUCCESS;
-}
-
-// The digest launch and the flow coalesce launches of a checked, non-empty device-resident batch on
-// `stream`. `copied_at` (nullable): where in the context's scratch the count of written payload bytes lies.
-static fs_status flows_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
-                               uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
-                               fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
-                               fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, hipStream_t stream,
-                               uint64_t* copied_at) {
-    const framesum::FlowScratch s = framesum::flows_scratch(n);
-    if (s.sort_bytes == 0) return set_err(ctx, FS_E_HIP, "fs_coalesce_flows_batch: the sort reports no temporary storage size");
-    fs_status st = segment_grow(ctx, &ctx->fl_scratch, &ctx->fl_cap_scratch, s.bytes);
-    if (st == FS_SUCCESS && (!out || !status)) st = segment_grow(ctx, &ctx->co_results, &ctx->co_cap_results, (uint64_t)n * 9);
-    if (st != FS_SUCCESS) return st;
-    if (!out) out = reinterpret_cast<fs_digest*>(ctx->co_results);
-    if (!status) status = ctx->co_results + (uint64_t)n * 8;
-    if (copied_at) *copied_at = s.copied;
-    if (ctx->flow_steps == framesum::kFlowStepsAll)
-        FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, stream,
-                           (flags & FS_RX_FCS) ? framesum::FsOp::kFcs : framesum::FsOp::kDigest, nullptr, 0));
-    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
-    FS_HIP(ctx, framesum::launch_coalesce_flows(frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, flows,
-                                                order, run_of, totals, ctx->fl_scratch, s, ctx->flow_hash_mask, wgs,
-                                                ctx->flow_steps, stream));
-    return FS_SUCCESS;
-}
-
-fs_status fs_coalesce_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
-                                  uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
-                                  fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
-                                  fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
-    if (!ctx) return FS_E_INVALID;
-    ctx->err.clear();
-    const fs_status st = flows_check(ctx, "fs_coalesce_flows_batch", frames, offsets, lengths, n, flags, payload,
-                                     payload_cap, runs, order, totals, true);
-    if (st != FS_SUCCESS) return st;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    if (n == 0) {
-        FS_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(fs_rx_flow_totals), reinterpret_cast<hipStream_t>(stream)));
-        return FS_SUCCESS;
-    }
-    return flows_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, payload, payload_cap, runs, flows, order, run_of,
-                         totals, out, status, reinterpret_cast<hipStream_t>(stream), nullptr);
-}
-
-fs_status fs_coalesce_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes,
-                                       const uint64_t* offsets, const uint32_t* lengths, uint32_t n, uint32_t mtu,
-                                       uint32_t flags, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
-                                       fs_rx_flow* flows, uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals,
-                                       fs_digest* out, uint8_t* status) {
-    if (!ctx) return FS_E_INVALID;
-    ctx->err.clear();
-    const fs_status ast = flows_check(ctx, "fs_coalesce_flows_batch_host", frames, offsets, lengths, n, flags, payload,
-                                      payload_cap, runs, order, totals, false);
-    if (ast != FS_SUCCESS) return ast;
-    if (n == 0) {
-        std::memset(totals, 0, sizeof(fs_rx_flow_totals));
-        return FS_SUCCESS;
-    }
-    const uint32_t bad = framesum::plan::first_frame_out_of_range(offsets, lengths, n, frames_bytes);
-    if (bad < n)
-        return set_err(ctx, FS_E_INVALID,
-                       "fs_coalesce_flows_batch_host: frame " + std::to_string(bad) + " ends past frames_bytes");
-    // the staged span [lo, hi), and the most payload the batch can hold
-    uint64_t lo = UINT64_MAX, hi = 0, most = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t o = offsets[i], e = o + lengths[i];
-        lo = o < lo ? o : lo;
-        hi = e > hi ? e : hi;
-        most += lengths[i];
-    }
-    const uint64_t d_cap = payload_cap < most ? payload_cap : most;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    fs_status st = quiesce_host_streams(ctx);
-    if (st != FS_SUCCESS) return st;
-    uint64_t cpy_lo, cpy_hi;
-    framesum::plan::copy_span(lo, hi, frames_bytes, cpy_lo, cpy_hi);
-    HostSlot& sl = ctx->slot[0];
-    st = ensure_slot(ctx, sl, cpy_hi - cpy_lo + 64, n);
-    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->co_d_payload, &ctx->co_cap_payload, d_cap);
-    // totals (24), then per frame: a run (24), a flow (32), order (4), run_of (4)
-    if (st == FS_SUCCESS) st = segment_grow(ctx, &ctx->fl_d_arrays, &ctx->fl_cap_arrays, (uint64_t)n * 64 + 24);
-    if (st != FS_SUCCESS) return st;
-    ctx->host_dirty = true;  // until this call has waited for all of its work
-    const hipStream_t ks = ctx->compute_stream;
-    fs_rx_flow_totals* d_totals = reinterpret_cast<fs_rx_flow_totals*>(ctx->fl_d_arrays);
-    fs_rx_run* d_runs = reinterpret_cast<fs_rx_run*>(ctx->fl_d_arrays + 24);
-    fs_rx_flow* d_flows = reinterpret_cast<fs_rx_flow*>(ctx->fl_d_arrays + 24 + (uint64_t)n * 24);
-    uint32_t* d_order = reinterpret_cast<uint32_t*>(ctx->fl_d_arrays + 24 + (uint64_t)n * 56);
-    uint32_t* d_run_of = reinterpret_cast<uint32_t*>(ctx->fl_d_arrays + 24 + (uint64_t)n * 60);
-    if (sl.used) FS_HIP_DRAIN(ctx, hipStreamWaitEvent(ks, sl.consumed, 0));
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_frames, frames + cpy_lo, cpy_hi - cpy_lo, hipMemcpyHostToDevice, ks));
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_offsets, offsets, (size_t)n * 8, hipMemcpyHostToDevice, ks));
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(sl.d_lengths, lengths, (size_t)n * 4, hipMemcpyHostToDevice, ks));
-    const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(sl.d_frames) - cpy_lo);
-    uint64_t copied_at = 0;
-    st = flows_enqueue(ctx, base, sl.d_offsets, sl.d_lengths, n, mtu, flags, ctx->co_d_payload, d_cap, d_runs,
-                       flows ? d_flows : nullptr, d_order, run_of ? d_run_of : nullptr, d_totals, sl.d_out, sl.d_status, ks,
-                       &copied_at);
-    if (st != FS_SUCCESS) {
-        drain_host_streams(ctx);
-        return st;
-    }
-    // the totals and how far the payload got written decide what else comes back
-    fs_rx_flow_totals t;
-    uint64_t copied = 0;
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&t, d_totals, sizeof t, hipMemcpyDeviceToHost, ks));
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&copied, ctx->fl_scratch + copied_at, 8, hipMemcpyDeviceToHost, ks));
-    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
-    if (copied > d_cap || t.n_accepted > n || t.n_runs > t.n_accepted || t.n_flows > t.n_runs) {
-        drain_host_streams(ctx);
-        return set_err(ctx, FS_E_HIP, "fs_coalesce_flows_batch_host: inconsistent totals from the device");
-    }
-    if (copied) FS_HIP_DRAIN(ctx, hipMemcpyAsync(payload, ctx->co_d_payload, copied, hipMemcpyDeviceToHost, ks));
-    if (t.n_runs) FS_HIP_DRAIN(ctx, hipMemcpyAsync(runs, d_runs, (size_t)t.n_runs * sizeof(fs_rx_run), hipMemcpyDeviceToHost, ks));
-    if (flows && t.n_flows)
-        FS_HIP_DRAIN(ctx, hipMemcpyAsync(flows, d_flows, (size_t)t.n_flows * sizeof(fs_rx_flow), hipMemcpyDeviceToHost, ks));
-    if (t.n_accepted) FS_HIP_DRAIN(ctx, hipMemcpyAsync(order, d_order, (size_t)t.n_accepted * 4, hipMemcpyDeviceToHost, ks));
-    if (run_of) FS_HIP_DRAIN(ctx, hipMemcpyAsync(run_of, d_run_of, (size_t)n * 4, hipMemcpyDeviceToHost, ks));
-    if (out) FS_HIP_DRAIN(ctx, hipMemcpyAsync(out, sl.d_out, (size_t)n * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
-    if (status) FS_HIP_DRAIN(ctx, hipMemcpyAsync(status, sl.d_status, n, hipMemcpyDeviceToHost, ks));
-    FS_HIP_DRAIN(ctx, hipEventRecord(sl.consumed, ks));
-    sl.used = true;
-    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
-    ctx->host_dirty = false;
-    *totals = t;
     return FS_SUCCESS;
 }
 

@@ -1,0 +1,179 @@
+// Internal to the host side of the C ABI (framesum_api.cpp: context lifecycle, digest and fill calls;
+// framesum_api_tx.cpp: the TX frame build; framesum_api_rx.cpp: the two RX coalesce families): the
+// context, the error helpers and macros, the grow-only device buffer, and the staging helpers of the
+// host-staged calls that stage one batch through slot 0. Defined in framesum_api.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/framesum.h"
+#include "framesum_internal.h"
+#include "framesum_plan.h"
+
+// Host-staged path: the batch is cut into chunks of about kChunkBytes of frame bytes,
+// staged through kHostSlots device buffers. The whole batch's descriptors go first, in one
+// H2D copy; the chunks' frame bytes then alternate between two copy streams (two DMA queues
+// keep the PCIe link busier than one: no gap between one chunk's copy and the next); kernels
+// and the small D2H copies run on a compute stream. Events order each chunk's kernel after
+// its copy (`copied`) and the reuse of a slot by chunk c + kHostSlots after chunk c's kernel
+// (`consumed`), so chunk c+1's H2D overlaps chunk c's kernel and D2H.
+constexpr int kHostSlots = 3;
+constexpr uint64_t kChunkBytes = 16ull << 20;
+constexpr uint32_t kChunkFrames = 1u << 20;
+// Frames per call: tile and frame indices are 32-bit in the kernel (n + 15 must not wrap).
+constexpr uint32_t kMaxFrames = 1u << 31;
+
+// A grow-only device buffer, freed with the context.
+struct DevBuf {
+    uint8_t* p = nullptr;
+    uint64_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    // At least `bytes` bytes (and 256 more: the kernels read past frame ends), the contents lost when
+    // it grows; `what` names the buffer in the FS_E_NOMEM message.
+    fs_status grow(fs_ctx* ctx, uint64_t bytes, const char* what = "hipMalloc of a staging buffer");
+    void release();
+    template <class T>
+    T* as(uint64_t at = 0) const { return reinterpret_cast<T*>(p + at); }
+};
+
+struct HostSlot {
+    hipEvent_t copied = nullptr, consumed = nullptr, landed = nullptr;  // landed: the chunk's results are in the mirror
+    bool used = false;
+    DevBuf frames, offsets, lengths, out, status;
+};
+
+// fs_segment_batch stages each call's sends in a block of its own: pinned host memory the call
+// fills, a device copy the kernel reads, and an event recorded behind the kernel. A block is
+// refilled only once its event has completed, so calls need no synchronization between them.
+constexpr int kSegStages = 32;
+struct SegStage {
+    uint8_t* h = nullptr;
+    uint8_t* d = nullptr;
+    uint64_t cap = 0;
+    hipEvent_t done = nullptr;
+    bool used = false;
+};
+
+struct fs_ctx {
+    int device = 0;
+    int num_cus = 0;
+    framesum::FsTables* d_tables = nullptr;
+    // fault injection for the host-staged pipeline's tests, settable only through the test
+    // library's fs_test_set_fault (-DFS_TEST_HOOKS): fs_digest_batch_host fails with FS_E_NOMEM at
+    // chunk k, after the earlier chunks' work and chunk k's copy are queued. -1 in the product.
+    long fault_chunk = -1;
+    // the path the latest fs_digest_batch_host took (fs_test_last_host_path): 1 staged in one
+    // chunk, 2 read in place, 3 chunked
+    int last_host_path = 0;
+    // the host-mapped block the kernels post their reports to (framesum_choice.h), and what the
+    // context remembers of them between launches
+    volatile uint32_t* h_report = nullptr;
+    uint32_t* d_report = nullptr;
+    framesum::ChoiceState choice;
+    int force_kernel = 0;  // fs_ctx_set_kernel
+    int workgroups = 0;    // fs_ctx_set_workgroups (0: one per CU)
+    HostSlot slot[kHostSlots];
+    hipStream_t copy_stream = nullptr, compute_stream = nullptr;
+    hipStream_t copy_stream2 = nullptr;  // the odd chunks' frame copies
+    hipEvent_t desc_copied = nullptr;    // the batch's descriptors are on the device
+    hipEvent_t host_done = nullptr;      // a host-staged call's last device work (polled, host_wait)
+    // a host-staged call left work in flight (it failed half-way): the next one drains the
+    // context's streams first (begin_host_call); a call that returns FS_SUCCESS leaves none
+    bool host_dirty = false;
+    DevBuf desc;  // the batch's offsets (8 n) then lengths (4 n)
+    // pinned host mirrors of the descriptors and results, so every per-chunk copy is
+    // asynchronous even when the caller's arrays are pageable (Go slices, numpy)
+    uint8_t* h_pin = nullptr;
+    uint8_t* d_pin = nullptr;  // h_pin as the device addresses it (mapped): kernels write results there
+    uint64_t cap_pin_n = 0;
+    // TX frame build: the kernel's table basis (built on the first call), the staging blocks, and
+    // the device buffers of fs_segment_batch_host (payload, frames, the four result arrays)
+    framesum::SegTables* d_seg_tables = nullptr;
+    SegStage seg_stage[kSegStages];
+    int seg_next = 0;  // the block to wait for when all are busy
+    DevBuf seg_payload, seg_frames, seg_arrays;
+    // RX coalesce: the kernels' scratch, out / status when the caller passes none, and the device
+    // buffers of fs_coalesce_batch_host (payload; totals, runs and run_of)
+    DevBuf co_scratch, co_results, co_payload, co_arrays;
+    // flow-aware RX coalesce: the kernels' scratch and the device result arrays of
+    // fs_coalesce_flows_batch_host (out / status and the payload share the buffers above). The hash
+    // mask and the steps are all ones / all steps unless the test library's setters change them.
+    DevBuf fl_scratch, fl_arrays;
+    uint32_t flow_hash_mask = 0xFFFFFFFFu;
+    uint32_t flow_steps = framesum::kFlowStepsAll;
+    std::string err;
+};
+
+namespace framesum {
+namespace host {
+
+// The message fs_last_error gives for `ctx`, or for the calling thread (g_create_err) when ctx is null
+// (fs_ctx_create, fs_segment_layout); returns `code`.
+extern thread_local std::string g_create_err;
+fs_status set_err(fs_ctx* ctx, fs_status code, const std::string& msg);
+fs_status hip_err(fs_ctx* ctx, hipError_t e, const char* what);
+
+#define FS_HIP(ctx, call)                                                      \
+    do {                                                                       \
+        hipError_t e_ = (call);                                                \
+        if (e_ != hipSuccess) return framesum::host::hip_err(ctx, e_, #call);  \
+    } while (0)
+
+// Every host-staged entry point starts here, behind hipSetDevice of the context's device: the pinned
+// mirrors and the staging slots are free only once the context's compute stream AND both copy streams
+// are idle (a host-staged call that failed half-way may have left odd-chunk copies in flight on
+// copy_stream2 that would otherwise write a slot while the next call stages into it). A call that
+// succeeded left nothing in flight (its results were waited for), so the three synchronizes (~3 us each
+// when idle) run only after a failed call.
+fs_status begin_host_call(fs_ctx* ctx);
+
+// A host-staged call that fails after it has enqueued work drains the context's streams before it
+// returns (best effort), so that nothing of it still reads the caller's buffers or writes the
+// caller's result arrays (the kernel writes them in place when they are pinned) after the error.
+void drain_host_streams(fs_ctx* ctx);
+#define FS_HIP_DRAIN(ctx, call)                          \
+    do {                                                 \
+        hipError_t e_ = (call);                          \
+        if (e_ != hipSuccess) {                          \
+            framesum::host::drain_host_streams(ctx);     \
+            return framesum::host::hip_err(ctx, e_, #call); \
+        }                                                \
+    } while (0)
+
+// One launch of the context's kernel choice.
+// `force` < 0: the context's kernel choice (fs_ctx_set_kernel).
+hipError_t launch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
+                  uint32_t mtu, fs_digest* out, uint8_t* status, hipStream_t stream, FsOp op, uint8_t* wframes,
+                  uint32_t tx, int force = -1);
+
+// Grow-only staging of one slot; a slot being regrown first waits for its last kernel.
+fs_status ensure_slot(fs_ctx* ctx, HostSlot& sl, uint64_t frame_bytes, uint32_t n);
+
+// A host-staged call that stages its whole batch through slot 0 and runs on the compute stream `ks`
+// (fs_fill_batch_host and the two RX coalesce host calls): where the batch lies on the device. The
+// kernels address frame i at base + offsets[i]: base = staging - cpy_lo (4-B aligned).
+struct Staged {
+    HostSlot* sl;
+    hipStream_t ks;
+    uint8_t* base;
+    const uint64_t* d_off;
+    const uint32_t* d_len;
+    fs_digest* d_out;
+    uint8_t* d_st;
+};
+// Behind begin_host_call: the frames' span [lo, hi) (plan::copy_span of it) and the descriptors into
+// slot 0, behind the slot's last kernel. Pinned `offsets` and `lengths` (fs_host_alloc, the context's
+// mirror) are copied from directly; pageable memory goes through the runtime's own pinned staging.
+// The context is dirty from the first copy queued; a later failure drains.
+fs_status stage_batch(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, uint64_t lo, uint64_t hi,
+                      const uint64_t* offsets, const uint32_t* lengths, uint32_t n, Staged& s);
+// ... and behind the call's last enqueue: the slot is marked as read by this call's kernels, and
+// everything queued is waited for.
+fs_status finish_staged(fs_ctx* ctx, const Staged& s);
+
+}  // namespace host
+}  // namespace framesum

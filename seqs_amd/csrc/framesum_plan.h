@@ -106,7 +106,8 @@ inline uint32_t first_frame_out_of_range(const uint64_t* offsets, const uint32_t
 // [0, frames_bytes) (overflow-safe), the longest frame, and the byte span [lo, hi) of the whole
 // batch. Branch-free in the loop (the compiler vectorizes it): the host-staged call of a batch of
 // short frames walks 65,536 descriptors per call, and two passes of a branchy loop were a sizeable
-// part of its host time. bad = the first out-of-range frame, or n.
+// part of its host time. bad = the first out-of-range frame, or n. `extra`: bytes
+// behind every frame that must lie in range too (the FCS a TX fill appends); hi does not count them.
 struct Scan {
     uint32_t bad, max_len, min_len;
     uint64_t lo, hi;
@@ -155,6 +156,15 @@ inline Scan scan_from(const ScanCore& c, const uint64_t* offsets, const uint32_t
 inline Scan scan_batch(const uint64_t* offsets, const uint32_t* lengths, uint32_t n, uint64_t frames_bytes,
                        uint32_t extra = 0) {
     return scan_from(scan_core(offsets, lengths, n), offsets, lengths, n, frames_bytes, extra);
+}
+
+// The sum of a batch's lengths: the bytes fs_digest_batch_multi balances over its contexts, and the
+// most payload an RX coalesce of the batch can deliver. (Apart from scan_core, whose reductions are
+// the timed loop of fs_digest_batch_host.)
+inline uint64_t total_length(const uint32_t* lengths, uint32_t n) {
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) total += lengths[i];
+    return total;
 }
 
 struct Chunk {
@@ -230,8 +240,7 @@ inline void multi_blocks(const uint64_t* offsets, const uint32_t* lengths, uint3
         std::stable_sort(p.order.begin(), p.order.end(),
                          [offsets](uint32_t a, uint32_t b) { return offsets[a] < offsets[b]; });
     }
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) total += lengths[i];
+    const uint64_t total = total_length(lengths, n);
     // block k starts at the first position whose running byte count reaches k/nctx of the total
     uint64_t run = 0;
     int k = 1;

@@ -201,6 +201,85 @@ static void check_high_offsets(std::mt19937_64& rng) {
     }
 }
 
+// What the single-slot host calls take from the plan (fs_fill_batch_host with the 4 FCS bytes as
+// `extra`, the RX coalesce host calls with total_length): the span and the range check with `extra`
+// at the buffer's very end, beyond 4 GiB and near 2^64, and the sum of the lengths.
+static void check_extra_span_and_total(std::mt19937_64& rng) {
+    const uint64_t G = uint64_t(1) << 32;
+    for (uint64_t base : {uint64_t(0), G + 4096, 5 * G + 3, UINT64_MAX - (uint64_t(1) << 34)}) {
+        // the last frame in memory is frame 1; frame 2 lies lowest
+        std::vector<uint64_t> off = {base + 1000, base + 5000, base + 7};
+        std::vector<uint32_t> len = {60, 1500, 0};
+        const uint64_t end = base + 6500;
+        for (uint32_t extra : {0u, 4u}) {
+            const Scan sc = scan_batch(off.data(), len.data(), 3, end + extra, extra);  // ends exactly at frames_bytes
+            CHECK(sc.bad == 3 && sc.lo == base + 7 && sc.hi == end && sc.max_len == 1500 && sc.min_len == 0);
+            CHECK(sc.hi + extra == end + extra);  // the fill's copied-back span ends behind the last FCS
+            CHECK(first_frame_out_of_range(off.data(), len.data(), 3, end + extra, extra) == 3);
+            const Scan past = scan_batch(off.data(), len.data(), 3, end + extra - 1, extra);  // one past frames_bytes
+            CHECK(past.bad == 1 && past.lo == base + 7 && past.hi == end);
+            CHECK(first_frame_out_of_range(off.data(), len.data(), 3, end + extra - 1, extra) == 1);
+        }
+        // the frame itself fits, its 4 extra bytes alone overrun: by 4, 3, 2, 1 bytes, then not at all
+        for (uint32_t room = 0; room <= 4; ++room)
+            CHECK(scan_batch(off.data(), len.data(), 3, end + room, 4).bad == (room < 4 ? 1u : 3u));
+        // the staged copy of that span: from 16 B below the lowest frame (16-B aligned) to the buffer's end
+        uint64_t lo = 0, hi = 0;
+        copy_span(base + 7, end + 4, end + 4, lo, hi);
+        CHECK(lo == ((base + 7 >= 16 ? base + 7 - 16 : 0) & ~uint64_t(15)) && hi == end + 4 && lo <= base + 7);
+    }
+    {   // frames_bytes near 2^64: the per-frame fall-back of scan_from, with and without `extra`
+        std::vector<uint64_t> off = {UINT64_MAX - 100, UINT64_MAX - 5000};
+        std::vector<uint32_t> len = {96, 1500};
+        CHECK(scan_batch(off.data(), len.data(), 2, UINT64_MAX, 4).bad == 2);       // ends at 2^64 - 1 exactly
+        CHECK(scan_batch(off.data(), len.data(), 2, UINT64_MAX - 1, 4).bad == 0);   // one past
+        CHECK(scan_batch(off.data(), len.data(), 2, UINT64_MAX - 1, 0).bad == 2);
+        CHECK(scan_batch(off.data(), len.data(), 2, UINT64_MAX - 5, 0).bad == 0);
+        const Scan sc = scan_batch(off.data(), len.data(), 2, UINT64_MAX, 4);
+        CHECK(sc.lo == UINT64_MAX - 5000 && sc.hi == UINT64_MAX - 4);
+        len[0] = 97;  // offset + length + extra = 2^64 + 1: wraps, and must not pass
+        CHECK(scan_batch(off.data(), len.data(), 2, UINT64_MAX, 4).bad == 0);
+        CHECK(first_frame_out_of_range(off.data(), len.data(), 2, UINT64_MAX, 4) == 0);
+    }
+    // total_length: empty, one frame, a sum past 2^32, random batches against a plain loop
+    CHECK(total_length(nullptr, 0) == 0);
+    {
+        const std::vector<uint32_t> big(5, UINT32_MAX);
+        CHECK(total_length(big.data(), 1) == UINT32_MAX && total_length(big.data(), 5) == 5 * uint64_t(UINT32_MAX));
+    }
+    for (int kind = 0; kind < 5; ++kind)
+        for (uint32_t n : {1u, 64u, 1000u}) {
+            const Batch b = make_batch(rng, n, kind);
+            uint64_t sum = 0;
+            for (uint32_t l : b.len) sum += l;
+            CHECK(total_length(b.len.data(), n) == sum);
+        }
+}
+
+// The batch tests/test_gpu_host_calls.py fails a digest on at its second chunk: 128 frames of
+// 64..1500 B in two groups of 64, the second more than 16 MiB behind the first, in 17 MiB. With the
+// library's chunk parameters it is two chunks, [0, 64) and [64, 128): the second group does not fit
+// the first chunk's 16 MiB, and a chunk of 64 frames does not take the rest.
+static void check_two_chunk_batch() {
+    Batch b;
+    uint64_t pos = 0;
+    for (uint32_t i = 0; i < 128; ++i) {
+        if (i == 64) pos = (uint64_t(16) << 20) + 65536;
+        b.len.push_back(64 + (i * 379) % 1437);
+        b.off.push_back(pos);
+        pos += (b.len[i] + 3) & ~3u;
+    }
+    b.bytes = uint64_t(17) << 20;
+    CHECK(pos <= b.bytes);
+    const Scan sc = scan_batch(b.off.data(), b.len.data(), 128, b.bytes);
+    CHECK(sc.bad == 128 && sc.min_len >= 64 && sc.max_len <= 1500 && sc.hi - sc.lo > (uint64_t(16) << 20));
+    check_chunks(b, uint64_t(16) << 20, 1u << 20);
+    std::vector<Chunk> ch;
+    host_chunks(b.off.data(), b.len.data(), 128, b.bytes, uint64_t(16) << 20, 1u << 20, ch);
+    CHECK(ch.size() == 2 && ch[0].c0 == 0 && ch[0].c1 == 64 && ch[1].c0 == 64 && ch[1].c1 == 128);
+    CHECK(ch.size() == 2 && ch[0].cpy_lo == 0 && ch[1].cpy_lo == (uint64_t(16) << 20) + 65536 - 16);
+}
+
 static void check_shards(uint64_t n, uint32_t N) {
     uint64_t sum = 0;
     for (uint32_t k = 0; k < N; ++k) sum += shard_count(n, N, k);
@@ -355,6 +434,8 @@ int main() {
         CHECK(scan_batch(off.data(), len.data(), 0, 14).bad == 0);
     }
     check_high_offsets(rng);
+    check_extra_span_and_total(rng);
+    check_two_chunk_batch();
     // multi blocks: more contexts than frames, empty batches, unordered and overlapping batches
     for (int kind = 0; kind < 5; ++kind)
         for (uint32_t n : {0u, 1u, 3u, 8u, 9u, 100u, 4097u})
