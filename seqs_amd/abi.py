@@ -1,0 +1,156 @@
+"""The framesum C ABI (include/framesum.h) as ctypes sees it: constants, record layouts, the
+prototype table and the library loader. No torch here: seqs_amd/framesum.py builds the calls on it.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from typing import Optional
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_LIB_PATH = os.environ.get("FRAMESUM_LIB") or os.path.join(_HERE, "lib", "libframesum.so")
+
+# The test library: the same sources built with -DFS_TEST_HOOKS (seqs_amd/csrc/Makefile), which adds
+# the fault-injection setters fs_test_set_fault / fs_test_group_set_fault. Only tests load it; the
+# product library has no such hook (and reads no environment variable for one).
+TEST_LIB_PATH = os.path.join(_HERE, "lib", "test", "libframesum_test.so")
+
+FS_SUCCESS = 0
+FS_E_INVALID = -1
+FS_E_HIP = -2
+FS_E_NOMEM = -3
+FS_E_NODEVICE = -4
+
+# fs_verdict (include/framesum.h) — RecvEth error classes (stacks/portstack.go:120-142).
+VERDICTS = {
+    0: "OK",
+    1: "errPacketSmol",
+    2: "errPacketExceedsMTU",
+    3: "ignored (not IPv4/ARP)",
+    4: "ARP",
+    5: "errIPVersion",
+    6: "errInvalidIHL",
+    7: "errBadIPTotalLenOrIHL",
+    8: "errUnknownIPProto",
+    9: "errTooShortTCPOrUDP",
+    10: "errZeroPort",
+    11: "errBadUDPLength",
+    12: "errBadTCPOffset",
+    13: "ErrChecksumTCPorUDP",
+    14: "FCS missing or wrong (fs_digest_batch_fcs)",
+}
+
+# fs_fill_batch flags
+FILL_CSUM = 1
+FCS_APPEND = 2
+FS_ERR_FCS = 14
+# fs_coalesce_batch flag: the frames carry their 4-byte FCS
+RX_FCS = 1
+NO_RUN = 0xFFFFFFFF  # run_of of a frame that was not accepted
+
+DIGEST_DTYPE = np.dtype([("crc32", "<u4"), ("ip_csum", "<u2"), ("l4_csum", "<u2")])
+# fs_tx_send: one send of the TX frame build (72 bytes, no padding)
+SEND_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("payload_off", "<u8"), ("payload_len", "<u4"),
+                       ("reserved", "<u4")])
+SEGMENT_MAX_FRAMES = 4096
+# fs_rx_run: one run of the RX coalesce (24 bytes, no padding), and fs_rx_totals (16 bytes)
+RUN_DTYPE = np.dtype([("payload_off", "<u8"), ("payload_len", "<u4"), ("first_frame", "<u4"), ("n_frames", "<u4"),
+                      ("tcp_flags", "u1"), ("reserved", "u1", (3,))])
+TOTALS_DTYPE = np.dtype([("payload_bytes", "<u8"), ("n_runs", "<u4"), ("reserved", "<u4")])
+# fs_rx_flow: one flow of the flow-aware RX coalesce (32 bytes, no padding), and fs_rx_flow_totals (24 bytes)
+FLOW_DTYPE = np.dtype([("payload_off", "<u8"), ("payload_len", "<u8"), ("first_run", "<u4"), ("n_runs", "<u4"),
+                       ("first_frame", "<u4"), ("n_frames", "<u4")])
+FLOW_TOTALS_DTYPE = np.dtype([("payload_bytes", "<u8"), ("n_runs", "<u4"), ("n_flows", "<u4"), ("n_accepted", "<u4"),
+                              ("reserved", "<u4")])
+
+
+class FramesumError(RuntimeError):
+    pass
+
+
+_st, _int, _u32, _u64, _str = ctypes.c_int32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_char_p
+_p = ctypes.c_void_p  # any pointer, and hipStream_t
+_pp, _pu64, _pint = ctypes.POINTER(_p), ctypes.POINTER(_u64), ctypes.POINTER(_int)
+
+# name -> (restype, argtypes): every function include/framesum.h declares, in its order (checked
+# against the header by tests/test_abi.py and tests/test_binding_prototypes.py).
+PROTOTYPES = {
+    "fs_abi_version": (_u32, []),
+    "fs_device_count": (_int, []),
+    "fs_ctx_create": (_st, [_int, _pp]),
+    "fs_ctx_destroy": (_st, [_p]),
+    "fs_last_error": (_str, [_p]),
+    "fs_digest_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _p, _p, _p]),
+    "fs_fill_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _u32, _p, _p, _p]),
+    "fs_fill_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _u32, _p, _p]),
+    "fs_segment_layout": (_st, [_p, _u32, _u32, _u32, _pu64, _pu64]),
+    "fs_segment_batch": (_st, [_p, _p, _u32, _p, _u64, _u32, _u32, _u32, _p, _u64, _p, _p, _p, _p, _p]),
+    "fs_segment_batch_host": (_st, [_p, _p, _u32, _p, _u64, _u32, _u32, _u32, _p, _u64, _p, _p, _p, _p]),
+    "fs_coalesce_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _u32, _p, _u64, _p, _p, _p, _p, _p, _p]),
+    "fs_coalesce_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _u32, _p, _u64, _p, _p, _p, _p, _p]),
+    "fs_coalesce_flows_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _u32, _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "fs_coalesce_flows_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _u32, _p, _u64, _p, _p, _p, _p, _p, _p, _p]),
+    "fs_digest_batch_fcs": (_st, [_p, _p, _p, _p, _u32, _u32, _p, _p, _p]),
+    "fs_digest_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _p, _p]),
+    "fs_digest_batch_multi": (_st, [_pp, _int, _p, _u64, _p, _p, _u32, _u32, _p, _p]),
+    "fs_group_create": (_st, [_pint, _int, _pp]),
+    "fs_group_destroy": (_st, [_p]),
+    "fs_group_last_error": (_str, [_p]),
+    "fs_shard_count": (_u64, [_u64, _u32, _u32]),
+    "fs_digest_batch_sharded": (_st, [_p, _pp, _pp, _pp, _u64, _u32, _p, _p]),
+    "fs_shard_slab_bytes": (_u64, [_u64, _u32]),
+    "fs_deinterleave": (_st, [_p, _p, _u32, _u64, _p, _p, _p]),
+    "fs_ctx_set_kernel": (_st, [_p, _int]),
+    "fs_ctx_last_kernel": (_int, [_p]),
+    "fs_ctx_set_workgroups": (_st, [_p, _int]),
+    "fs_host_alloc": (_st, [_p, _u64, _pp]),
+    "fs_host_free": (_st, [_p, _p]),
+}
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
+
+# Not in the header, set only where the loaded library has them: the test library's hooks
+# (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
+OPTIONAL_PROTOTYPES = {
+    "fs_test_set_fault": (_st, [_p, ctypes.c_long]),
+    "fs_test_group_set_fault": (_st, [_p, ctypes.c_long]),
+    "fs_test_group_set_fault_gather": (_st, [_p, ctypes.c_long]),
+    "fs_test_set_kernel_exact": (_st, [_p, _int]),
+    "fs_test_last_host_path": (_int, [_p]),
+    "fs_test_set_flow_hash_mask": (_st, [_p, _u32]),
+    "fs_test_set_flow_steps": (_st, [_p, _u32]),
+    "fs_debug_read_stamps": (_int, [_p, ctypes.c_size_t]),
+}
+# In the header, yet tolerated when absent: older builds of the library in same-box A/B runs lack it.
+_MAY_BE_ABSENT = ("fs_ctx_set_workgroups",)
+
+_lib = None
+_libs: dict = {}
+
+
+def lib_path() -> str:
+    return _LIB_PATH
+
+
+def load_library(path: Optional[str] = None) -> ctypes.CDLL:
+    """Load libframesum.so (raises if it was not built: no fallback path exists). `path`: another
+    build of the same ABI (the test library, TEST_LIB_PATH)."""
+    global _lib
+    if path is None and _lib is not None:
+        return _lib
+    p = path or _LIB_PATH
+    if p in _libs:
+        return _libs[p]
+    if not os.path.exists(p):
+        raise FramesumError(f"{p} is missing — run __graft_entry__.build() (or make -C seqs_amd/csrc)")
+    lib = ctypes.CDLL(p)
+    for name, (restype, argtypes) in {**PROTOTYPES, **OPTIONAL_PROTOTYPES}.items():
+        if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)  # (a missing product symbol raises here)
+        fn.restype, fn.argtypes = restype, argtypes
+    _libs[p] = lib
+    if path is None:
+        _lib = lib
+    return lib
