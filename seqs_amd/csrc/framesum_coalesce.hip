@@ -16,6 +16,9 @@
 //             alignment the source has (gfx950 serves global accesses at any byte address), the 0..15
 //             bytes in front of the first boundary and behind the last as one 1-, 2-, 4- and 8-byte
 //             access each. Exactly the payload's bytes are read and exactly its destination written.
+// The four steps are the gather steps of framesum_coalesce_dev.h, which fs_coalesce_flows_batch runs
+// too; here are the mode that makes them this call's (Plain: slot k of the scans is frame k, no
+// flows), the kernels by the names the traces know, and the launch.
 #include <hip/hip_runtime.h>
 
 #include "../../include/framesum.h"
@@ -27,7 +30,7 @@ namespace framesum {
 
 namespace {
 
-using namespace codev;  // the scan, the header load and the copy shared with framesum_flows.hip
+using namespace codev;  // the scan, the header load, the copy and the gather steps shared with framesum_flows.hip
 
 static_assert(sizeof(fs_rx_run) == 24 && sizeof(fs_rx_totals) == 16, "fs_rx_run / fs_rx_totals layout");
 
@@ -59,7 +62,6 @@ struct CoArgs {
     uint32_t n, n_blocks, fcs;
 };
 
-__device__ __forceinline__ Part zero_part() { return Part{0ull, 0u, 0u}; }
 __device__ __forceinline__ Part combine(const Part& a, const Part& b) {
     return Part{a.sum + b.sum, a.heads + b.heads, a.hidx1 > b.hidx1 ? a.hidx1 : b.hidx1};
 }
@@ -72,138 +74,36 @@ __device__ __forceinline__ Part shfl_up_part(const Part& v, int d) {
     return u;
 }
 
-__global__ void __launch_bounds__(kThreads) coalesce_classify(const CoArgs a) {
-    __shared__ Part s_part[kWaves];
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
-        const uint32_t i = blk * kScanBlock + threadIdx.x;
-        Hdr h, ph;
-        const Info f = classify_frame(a, i, h);
-        // the frame before: from the lane before, which has just classified it
-        Info pf;
-#pragma unroll
-        for (uint32_t k = 0; k < kHdrWords; ++k) ph.w[k] = __shfl_up(h.w[k], 1, 64);
-        const uint32_t packed = pack_info(f), bits = (f.accepted ? 1u : 0u) | (f.plain_tcp ? 2u : 0u);
-        const uint32_t ppacked = __shfl_up(packed, 1, 64), pbits = __shfl_up(bits, 1, 64);
-        pf.start = rec_start(ppacked);
-        pf.len = rec_len(ppacked);
-        pf.tcp_flags = rec_flags(ppacked);
-        pf.accepted = (pbits & 1u) != 0;
-        pf.plain_tcp = (pbits & 2u) != 0;
-        if (lane == 0) {  // ... except for a wave's first lane, which reads it itself
-            if (i > 0 && i < a.n) pf = classify_frame(a, i - 1, ph);
-            else pf = rejected();
-        }
-        const bool head = f.accepted && !joins(ph, pf, h, f);
-        if (i < a.n) a.rec[i] = make_uint2(packed, (f.accepted ? kAccepted : 0u) | (head ? kHead : 0u));
-        Part incl, excl, total;
-        block_scan(Part{f.accepted ? (uint64_t)f.len : 0ull, head ? 1u : 0u, head ? i + 1u : 0u}, s_part, incl, excl, total);
-        if (threadIdx.x == 0) a.partial[blk] = total;
+// The mode of the gather steps (framesum_coalesce_dev.h): slot k is frame k, and there are no flows.
+struct Plain {
+    using Part = framesum::Part;
+    struct Key {};
+    static constexpr uint32_t kFlowBit = 0;
+    static __device__ __forceinline__ Key key(const CoArgs&, uint32_t) { return Key{}; }
+    static __device__ __forceinline__ Key shfl_up_key(Key) { return Key{}; }
+    static __device__ __forceinline__ uint32_t frame(const CoArgs&, uint32_t k, Key) { return k; }
+    static __device__ __forceinline__ Part part(uint64_t len, bool head, bool, bool, uint32_t k) {
+        return Part{len, head ? 1u : 0u, head ? k + 1u : 0u};
     }
-}
-
-// One workgroup: prefix[b] = the partials of the workgroups before b; the totals.
-__global__ void __launch_bounds__(kThreads) coalesce_scan_partials(const CoArgs a) {
-    __shared__ Part s_part[kWaves];
-    Part carry = zero_part();
-    for (uint32_t base = 0; base < a.n_blocks; base += kScanBlock) {
-        const uint32_t b = base + threadIdx.x;
-        Part incl, excl, total;
-        block_scan(b < a.n_blocks ? a.partial[b] : zero_part(), s_part, incl, excl, total);
-        if (b < a.n_blocks) a.prefix[b] = combine(carry, excl);
-        carry = combine(carry, total);
-    }
-    if (threadIdx.x == 0) {
+    static __device__ __forceinline__ void write_totals(const CoArgs& a, const Part& carry) {
         fs_rx_totals t;
         t.payload_bytes = carry.sum;
         t.n_runs = carry.heads;
         t.reserved = 0;
         *a.totals = t;
-        *a.copied = carry.sum <= a.cap ? carry.sum : 0ull;
     }
-}
+};
 
-__global__ void __launch_bounds__(kThreads) coalesce_apply(const CoArgs a) {
-    __shared__ Part s_part[kWaves];
-    for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
-        const uint32_t i = blk * kScanBlock + threadIdx.x;
-        const uint2 r = i < a.n ? a.rec[i] : make_uint2(0u, 0u);
-        const bool acc = (r.y & kAccepted) != 0, head = (r.y & kHead) != 0;
-        const uint32_t len = acc ? rec_len(r.x) : 0u;
-        Part incl, excl, total;
-        block_scan(Part{(uint64_t)len, head ? 1u : 0u, head ? i + 1u : 0u}, s_part, incl, excl, total);
-        const Part base = a.prefix[blk];
-        const Part in = combine(base, incl);
-        const uint64_t off = base.sum + excl.sum;
-        if (i < a.n) {
-            const uint32_t run = acc ? in.heads - 1u : kNoRun;
-            a.payoff[i] = off;
-            a.runidx[i] = run;
-            a.hidx[i] = acc ? in.hidx1 - 1u : kNoRun;
-            if (a.run_of) a.run_of[i] = run;
-        }
-        // how far the packed buffer gets written when payload_cap cuts it short (the scan of the
-        // partials has set `copied` to the total when everything fits, else to 0): the end of the
-        // last frame below the cap. Only then do the waves meet at this one address.
-        if (a.totals->payload_bytes > a.cap) {
-            unsigned long long end = (acc && off + len <= a.cap) ? off + len : 0ull;
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) {
-                const uint32_t lo = __shfl_xor((uint32_t)end, m, 64), hi = __shfl_xor((uint32_t)(end >> 32), m, 64);
-                const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-                end = o > end ? o : end;
-            }
-            if ((threadIdx.x & 63u) == 0 && end != 0ull) atomicMax(a.copied, end);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(kThreads) coalesce_copy(const CoArgs a) {
-    const uint32_t sub = threadIdx.x & (kGroup - 1u), grp = threadIdx.x / kGroup;
-    const uint32_t n_tiles = (a.n + kTileFrames - 1u) / kTileFrames;
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint32_t i = tile * kTileFrames + grp;
-        if (i >= a.n) continue;
-        const uint2 r = a.rec[i];  // (three independent loads: one latency)
-        const uint64_t off = a.payoff[i];
-        const uint64_t at = a.offsets[i];
-        if (!(r.y & kAccepted)) continue;
-        const uint32_t len = rec_len(r.x);
-        if (len != 0 && off + len <= a.cap) copy_payload(a.payload + off, a.frames + at + rec_start(r.x), len, sub);
-        if (sub == 8) {
-            // a run ends where the next frame does not continue it (a continuing frame is accepted
-            // and no head); its last frame writes the record, behind its copy's loads and stores
-            const bool last = i + 1u == a.n || a.rec[i + 1u].y != kAccepted;
-            if (last) {
-                const uint32_t hd = a.hidx[i];
-                const uint64_t hoff = a.payoff[hd];
-                fs_rx_run run;
-                run.payload_off = hoff;
-                run.payload_len = (uint32_t)(off + len - hoff);
-                run.first_frame = hd;
-                run.n_frames = i - hd + 1u;
-                run.tcp_flags = (uint8_t)run_flags(rec_flags(a.rec[hd].x), rec_flags(r.x));
-                run.reserved[0] = run.reserved[1] = run.reserved[2] = 0;
-                a.runs[a.runidx[i]] = run;
-            }
-        }
-    }
-}
+__global__ void __launch_bounds__(kThreads) coalesce_classify(const CoArgs a) { gather_classify<Plain>(a); }
+__global__ void __launch_bounds__(kThreads) coalesce_scan_partials(const CoArgs a) { gather_scan_partials<Plain>(a); }
+__global__ void __launch_bounds__(kThreads) coalesce_apply(const CoArgs a) { gather_apply<Plain>(a); }
+__global__ void __launch_bounds__(kThreads) coalesce_copy(const CoArgs a) { gather_copy<Plain>(a); }
 
 }  // namespace
 
 CoScratch coalesce_scratch(uint32_t n) {
     CoScratch s;
-    const uint64_t nb = ((uint64_t)n + kScanBlock - 1) / kScanBlock;
-    uint64_t at = 0;
-    s.rec = at, at += 8ull * n;
-    s.payoff = at, at += 8ull * n;
-    s.partial = at, at += 16ull * nb;
-    s.prefix = at, at += 16ull * nb;
-    s.copied = at, at += 8;
-    s.runidx = at, at += 4ull * n;
-    s.hidx = at, at += 4ull * n;
-    s.bytes = at;
+    s.bytes = lay_run_arrays(s, lay_scan_arrays(s, 0, n, sizeof(Part)), n);
     return s;
 }
 
@@ -211,34 +111,14 @@ hipError_t launch_coalesce(const uint8_t* frames, const uint64_t* offsets, const
                            uint32_t flags, const uint8_t* status, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
                            uint32_t* run_of, fs_rx_totals* totals, uint8_t* scratch, int max_workgroups,
                            hipStream_t stream) {
-    const CoScratch s = coalesce_scratch(n);
     CoArgs a;
-    a.frames = frames;
-    a.offsets = offsets;
-    a.lengths = lengths;
-    a.status = status;
-    a.rec = reinterpret_cast<uint2*>(scratch + s.rec);
-    a.payoff = reinterpret_cast<uint64_t*>(scratch + s.payoff);
-    a.partial = reinterpret_cast<Part*>(scratch + s.partial);
-    a.prefix = reinterpret_cast<Part*>(scratch + s.prefix);
-    a.copied = reinterpret_cast<unsigned long long*>(scratch + s.copied);
-    a.runidx = reinterpret_cast<uint32_t*>(scratch + s.runidx);
-    a.hidx = reinterpret_cast<uint32_t*>(scratch + s.hidx);
-    a.payload = payload;
-    a.cap = payload_cap;
-    a.runs = runs;
-    a.run_of = run_of;
+    const GatherGrids g = fill_gather_args(a, frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, run_of,
+                                           scratch, coalesce_scratch(n), max_workgroups);
     a.totals = totals;
-    a.n = n;
-    a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
-    a.fcs = (flags & FS_RX_FCS) ? 4u : 0u;
-    const uint32_t cap = (uint32_t)(max_workgroups > 0 ? max_workgroups : 1);
-    const uint32_t n_tiles = (uint32_t)(((uint64_t)n + kTileFrames - 1) / kTileFrames);
-    const uint32_t g_scan = a.n_blocks < cap ? a.n_blocks : cap, g_copy = n_tiles < cap ? n_tiles : cap;
-    hipLaunchKernelGGL(coalesce_classify, dim3(g_scan), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(coalesce_classify, dim3(g.scan), dim3(kThreads), 0, stream, a);
     hipLaunchKernelGGL(coalesce_scan_partials, dim3(1), dim3(kThreads), 0, stream, a);
-    hipLaunchKernelGGL(coalesce_apply, dim3(g_scan), dim3(kThreads), 0, stream, a);
-    hipLaunchKernelGGL(coalesce_copy, dim3(g_copy), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(coalesce_apply, dim3(g.scan), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(coalesce_copy, dim3(g.copy), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 

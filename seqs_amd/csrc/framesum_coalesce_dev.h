@@ -1,7 +1,10 @@
-// Device code the two RX coalesce kernels files share (framesum_coalesce.hip: fs_coalesce_batch;
+// Device code the two RX coalesce kernel files share (framesum_coalesce.hip: fs_coalesce_batch;
 // framesum_flows.hip: fs_coalesce_flows_batch): the workgroup scan, loads and stores at any
-// alignment, a frame's header load and classification, and the payload copy by 16 lanes. HIP only;
-// the arithmetic these call is in framesum_coalesce.h, which compiles without HIP.
+// alignment, a frame's header load and classification, the payload copy by 16 lanes, and the four
+// gather steps -- classify, the scan of the partials, apply, copy -- written once over a mode that
+// each file supplies, with the launch arguments and the scratch layout the two families have in
+// common. (framesum_segment.hip takes Piece, load_at and store_at from here.) HIP only; the
+// arithmetic these call is in framesum_coalesce.h, which compiles without HIP.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -127,6 +130,216 @@ __device__ __forceinline__ void copy_payload(uint8_t* __restrict__ dst, const ui
     if (sub == 5 && (c.tail & 4u)) store_at<uint32_t>(dst + t0 + (c.tail & 8u), load_at<uint32_t>(src + t0 + (c.tail & 8u)));
     if (sub == 6 && (c.tail & 2u)) store_at<uint16_t>(dst + t0 + (c.tail & 12u), load_at<uint16_t>(src + t0 + (c.tail & 12u)));
     if (sub == 7 && (c.tail & 1u)) dst[t0 + (c.tail & 14u)] = src[t0 + (c.tail & 14u)];
+}
+
+// ---- The gather steps. Slot k of the scans and the copy stands for one frame; a run is a row of
+// slots whose frames continue each other. A mode M says which frame, and what else is kept:
+//   M::Part               the record the scans carry: sum (payload bytes), heads and hidx1 (run heads
+//                         and the last one's slot + 1; 0: none yet), and what the mode adds; P{} is
+//                         the zero, combine() and shfl_up_part() stand beside it
+//   M::part(len, head, fhead, acc, k)   slot k's
+//   M::Key, M::key(a, k), M::shfl_up_key(key)   what a slot knows beside its number: slot k's, read
+//                         from memory (k < a.n), and the lane before's; Key{} where there is no slot
+//   M::frame(a, k, key)   the frame slot k < a.n stands for
+//   M::write_totals(a, carry)           the call's totals from the scan's grand total
+//   M::kFlowBit           the bit of the slot record's y that says the slot opens a flow, and so a
+//                         run; 0: the mode has no flows and none of the following
+//   M::flow_head(a, k, acc, pacc, key, pkey)    does slot k open a flow?
+//   M::apply_extra(a, k, i, in, acc)    what apply writes per slot beside payoff, runidx, hidx, run_of
+//   M::flow_record(a, k, ny, off, len)  copy: lane 9 of slot k, ny = the next slot's y (0: none)
+// A: the kernel's arguments (fill_gather_args below names the fields these read).
+
+// One lane per slot: the slot record and the workgroup's partial.
+template <typename M, typename A>
+__device__ __forceinline__ void gather_classify(const A& a) {
+    using P = typename M::Part;
+    __shared__ P s_part[kWaves];
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
+        const uint32_t k = blk * kScanBlock + threadIdx.x;
+        const typename M::Key key = k < a.n ? M::key(a, k) : typename M::Key{};
+        const uint32_t i = k < a.n ? M::frame(a, k, key) : a.n;
+        Hdr h, ph;
+        const Info f = classify_frame(a, i, h);
+        // the slot before: from the lane before, which has just classified it
+        Info pf;
+#pragma unroll
+        for (uint32_t w = 0; w < kHdrWords; ++w) ph.w[w] = __shfl_up(h.w[w], 1, 64);
+        const uint32_t packed = pack_info(f), bits = (f.accepted ? 1u : 0u) | (f.plain_tcp ? 2u : 0u);
+        const uint32_t ppacked = __shfl_up(packed, 1, 64), pbits = __shfl_up(bits, 1, 64);
+        typename M::Key pkey = M::shfl_up_key(key);
+        pf.start = rec_start(ppacked);
+        pf.len = rec_len(ppacked);
+        pf.tcp_flags = rec_flags(ppacked);
+        pf.accepted = (pbits & 1u) != 0;
+        pf.plain_tcp = (pbits & 2u) != 0;
+        if (lane == 0) {  // ... except for a wave's first lane, which reads it itself
+            if (k > 0 && k < a.n) {
+                pkey = M::key(a, k - 1u);
+                pf = classify_frame(a, M::frame(a, k - 1u, pkey), ph);
+            } else {
+                pf = rejected();
+            }
+        }
+        bool fhead = false;
+        if constexpr (M::kFlowBit != 0) fhead = M::flow_head(a, k, f.accepted, pf.accepted, key, pkey);
+        const bool head = f.accepted && (fhead || !joins(ph, pf, h, f));
+        if (k < a.n)
+            a.rec[k] = make_uint2(packed, (f.accepted ? kAccepted : 0u) | (head ? kHead : 0u) | (fhead ? M::kFlowBit : 0u));
+        P incl, excl, total;
+        block_scan(M::part(f.accepted ? (uint64_t)f.len : 0ull, head, fhead, f.accepted, k), s_part, incl, excl, total);
+        if (threadIdx.x == 0) a.partial[blk] = total;
+    }
+}
+
+// One workgroup: prefix[b] = the partials of the workgroups before b; the totals.
+template <typename M, typename A>
+__device__ __forceinline__ void gather_scan_partials(const A& a) {
+    using P = typename M::Part;
+    __shared__ P s_part[kWaves];
+    P carry = P{};
+    for (uint32_t base = 0; base < a.n_blocks; base += kScanBlock) {
+        const uint32_t b = base + threadIdx.x;
+        P incl, excl, total;
+        block_scan(b < a.n_blocks ? a.partial[b] : P{}, s_part, incl, excl, total);
+        if (b < a.n_blocks) a.prefix[b] = combine(carry, excl);
+        carry = combine(carry, total);
+    }
+    if (threadIdx.x == 0) {
+        M::write_totals(a, carry);
+        *a.copied = carry.sum <= a.cap ? carry.sum : 0ull;
+    }
+}
+
+// The same workgroups as classify scan their records from their prefix: per slot its packed
+// position (64-bit), its run's index and its run's head (a max-scan of head slots).
+template <typename M, typename A>
+__device__ __forceinline__ void gather_apply(const A& a) {
+    using P = typename M::Part;
+    __shared__ P s_part[kWaves];
+    for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
+        const uint32_t k = blk * kScanBlock + threadIdx.x;
+        const uint2 r = k < a.n ? a.rec[k] : make_uint2(0u, 0u);
+        const bool acc = (r.y & kAccepted) != 0, head = (r.y & kHead) != 0, fhead = (r.y & M::kFlowBit) != 0;
+        const uint32_t len = acc ? rec_len(r.x) : 0u;
+        P incl, excl, total;
+        block_scan(M::part((uint64_t)len, head, fhead, acc, k), s_part, incl, excl, total);
+        const P base = a.prefix[blk];
+        const P in = combine(base, incl);
+        const uint64_t off = base.sum + excl.sum;
+        if (k < a.n) {
+            const uint32_t i = M::frame(a, k, M::key(a, k));
+            const uint32_t run = acc ? in.heads - 1u : kNoRun;
+            a.payoff[k] = off;
+            a.runidx[k] = run;
+            a.hidx[k] = acc ? in.hidx1 - 1u : kNoRun;
+            if constexpr (M::kFlowBit != 0) M::apply_extra(a, k, i, in, acc);
+            if (a.run_of && i < a.n) a.run_of[i] = run;
+        }
+        // how far the packed buffer gets written when payload_cap cuts it short (the scan of the
+        // partials has set `copied` to the total when everything fits, else to 0): the end of the
+        // last frame below the cap. Only then do the waves meet at this one address.
+        if (a.totals->payload_bytes > a.cap) {
+            unsigned long long end = (acc && off + len <= a.cap) ? off + len : 0ull;
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) {
+                const uint32_t lo = __shfl_xor((uint32_t)end, m, 64), hi = __shfl_xor((uint32_t)(end >> 32), m, 64);
+                const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+                end = o > end ? o : end;
+            }
+            if ((threadIdx.x & 63u) == 0 && end != 0ull) atomicMax(a.copied, end);
+        }
+    }
+}
+
+// The hot path: 16 lanes per slot. The destination advances with the slots; the source is wherever
+// the slot's frame lies. The last slot of a run writes the run's record, behind its copy.
+template <typename M, typename A>
+__device__ __forceinline__ void gather_copy(const A& a) {
+    const uint32_t sub = threadIdx.x & (kGroup - 1u), grp = threadIdx.x / kGroup;
+    const uint32_t n_tiles = (a.n + kTileFrames - 1u) / kTileFrames;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t k = tile * kTileFrames + grp;
+        if (k >= a.n) continue;
+        const uint2 r = a.rec[k];  // (loads that do not wait for the verdict: one latency, not two)
+        const uint64_t off = a.payoff[k];
+        const uint64_t at = a.offsets[M::frame(a, k, M::key(a, k))];
+        if (!(r.y & kAccepted)) continue;
+        const uint32_t len = rec_len(r.x);
+        if (len != 0 && off + len <= a.cap) copy_payload(a.payload + off, a.frames + at + rec_start(r.x), len, sub);
+        if (sub == 8 || (M::kFlowBit != 0 && sub == 9)) {
+            const uint32_t ny = k + 1u == a.n ? 0u : a.rec[k + 1u].y;
+            // a run ends where the next slot does not continue it (a continuing slot is accepted and
+            // no head of a run or a flow); its last slot writes the record
+            if (sub == 8 && ny != kAccepted) {
+                const uint32_t hd = a.hidx[k];
+                const uint64_t hoff = a.payoff[hd];
+                fs_rx_run run;
+                run.payload_off = hoff;
+                run.payload_len = (uint32_t)(off + len - hoff);
+                run.first_frame = hd;
+                run.n_frames = k - hd + 1u;
+                run.tcp_flags = (uint8_t)run_flags(rec_flags(a.rec[hd].x), rec_flags(r.x));
+                run.reserved[0] = run.reserved[1] = run.reserved[2] = 0;
+                a.runs[a.runidx[k]] = run;
+            }
+            if constexpr (M::kFlowBit != 0)
+                if (sub == 9) M::flow_record(a, k, ny, off, len);
+        }
+    }
+}
+
+// ---- The host side both families share. The fields of the kernel arguments the gather steps read
+// (`totals` and what a mode adds are the caller's), and the grids: `scan` for the kernels with one
+// lane per frame, `copy` for the copy, neither above max_workgroups.
+struct GatherGrids {
+    uint32_t scan, copy;
+};
+template <typename A, typename S>
+GatherGrids fill_gather_args(A& a, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
+                             uint32_t flags, const uint8_t* status, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
+                             uint32_t* run_of, uint8_t* scratch, const S& s, int max_workgroups) {
+    a.frames = frames;
+    a.offsets = offsets;
+    a.lengths = lengths;
+    a.status = status;
+    a.rec = reinterpret_cast<uint2*>(scratch + s.rec);
+    a.payoff = reinterpret_cast<uint64_t*>(scratch + s.payoff);
+    a.partial = reinterpret_cast<decltype(a.partial)>(scratch + s.partial);
+    a.prefix = reinterpret_cast<decltype(a.prefix)>(scratch + s.prefix);
+    a.copied = reinterpret_cast<unsigned long long*>(scratch + s.copied);
+    a.runidx = reinterpret_cast<uint32_t*>(scratch + s.runidx);
+    a.hidx = reinterpret_cast<uint32_t*>(scratch + s.hidx);
+    a.payload = payload;
+    a.cap = payload_cap;
+    a.runs = runs;
+    a.run_of = run_of;
+    a.n = n;
+    a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
+    a.fcs = (flags & FS_RX_FCS) ? 4u : 0u;
+    const uint32_t cap = (uint32_t)(max_workgroups > 0 ? max_workgroups : 1);
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)n + kTileFrames - 1) / kTileFrames);
+    return GatherGrids{a.n_blocks < cap ? a.n_blocks : cap, n_tiles < cap ? n_tiles : cap};
+}
+
+// The scratch of the gather steps from offset `at` on, in two rows (the flow family keeps its table
+// between them): the records, positions, partials of `part_bytes` each and `copied`; the run words.
+// Each returns the offset behind its row.
+template <typename S>
+uint64_t lay_scan_arrays(S& s, uint64_t at, uint64_t n, uint64_t part_bytes) {
+    const uint64_t nb = (n + kScanBlock - 1) / kScanBlock;
+    s.rec = at, at += 8ull * n;
+    s.payoff = at, at += 8ull * n;
+    s.partial = at, at += part_bytes * nb;
+    s.prefix = at, at += part_bytes * nb;
+    s.copied = at, at += 8;
+    return at;
+}
+template <typename S>
+uint64_t lay_run_arrays(S& s, uint64_t at, uint64_t n) {
+    s.runidx = at, at += 4ull * n;
+    s.hidx = at, at += 4ull * n;
+    return at;
 }
 
 }  // namespace codev

@@ -14,13 +14,16 @@
 //   sortkeys  one lane per frame: first frame of its flow << b | own index (framesum_flows.h).
 //   sort      rocprim::radix_sort_keys over the low 2 b + 1 bits: sorted[k] & mask is the frame at
 //             delivery slot k; the frames that are not accepted follow the accepted ones.
-//   classify, partials, apply
-//             fs_coalesce_batch's scans with slot k standing for frame sorted[k]: a wave's lanes hold
-//             consecutive slots and pass their header to the next lane. The scans also carry the flow
-//             heads, the last flow head's slot and the accepted count.
-//   copy      by slot, 16 lanes per slot: the destination advances sequentially, the source is
-//             wherever the slot's frame lies. The last slot of a run writes the run's record and the
-//             last slot of a flow the flow's, each behind its copy.
+//   classify, partials, apply, copy
+//             the gather steps of framesum_coalesce.hip (their one body is in framesum_coalesce_dev.h)
+//             in the mode ByFlow below: slot k stands for frame sorted[k], so a wave's lanes hold
+//             consecutive slots and pass their header to the next lane; a change of flow opens a run;
+//             the scans also carry the flow heads, the last flow head's slot and the accepted count;
+//             the copy's destination advances sequentially while its source is wherever the slot's
+//             frame lies, and the last slot of a flow writes the flow's record as the last slot of a
+//             run writes the run's, each behind its copy.
+// Here are the three kernels of the delivery order, that mode, the gather kernels by the names the
+// traces know, and the launch.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -206,60 +209,23 @@ __global__ void __launch_bounds__(kThreads) flows_sortkeys(const FlArgs a) {
     }
 }
 
-__global__ void __launch_bounds__(kThreads) flows_classify(const FlArgs a) {
-    __shared__ FlowPart s_part[kWaves];
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
-        const uint32_t k = blk * kScanBlock + threadIdx.x;
-        const uint64_t sk = k < a.n ? a.sorted[k] : ~0ull;
-        const uint32_t i = k < a.n ? flows::sort_index(sk, a.b) : a.n;
-        Hdr h, ph;
-        const Info f = classify_frame(a, i, h);
-        // the slot before: from the lane before, which has just classified it
-        Info pf;
-#pragma unroll
-        for (uint32_t w = 0; w < kHdrWords; ++w) ph.w[w] = __shfl_up(h.w[w], 1, 64);
-        const uint32_t packed = pack_info(f), bits = (f.accepted ? 1u : 0u) | (f.plain_tcp ? 2u : 0u);
-        const uint32_t ppacked = __shfl_up(packed, 1, 64), pbits = __shfl_up(bits, 1, 64);
-        uint64_t psk = shfl_up_u64(sk, 1);
-        pf.start = rec_start(ppacked);
-        pf.len = rec_len(ppacked);
-        pf.tcp_flags = rec_flags(ppacked);
-        pf.accepted = (pbits & 1u) != 0;
-        pf.plain_tcp = (pbits & 2u) != 0;
-        if (lane == 0) {  // ... except for a wave's first lane, which reads it itself
-            if (k > 0 && k < a.n) {
-                psk = a.sorted[k - 1u];
-                pf = classify_frame(a, flows::sort_index(psk, a.b), ph);
-            } else {
-                pf = rejected();
-            }
-        }
-        // the accepted frames come first, so an accepted slot behind slot 0 follows an accepted one
-        const bool fhead = f.accepted && (k == 0 || !pf.accepted || flows::sort_rep(psk, a.b) != flows::sort_rep(sk, a.b));
-        const bool head = f.accepted && (fhead || !joins(ph, pf, h, f));
-        if (k < a.n)
-            a.rec[k] = make_uint2(packed, (f.accepted ? kAccepted : 0u) | (head ? kHead : 0u) | (fhead ? flows::kFlowHead : 0u));
-        FlowPart incl, excl, total;
-        block_scan(FlowPart{f.accepted ? (uint64_t)f.len : 0ull, head ? 1u : 0u, head ? k + 1u : 0u, fhead ? 1u : 0u,
-                            fhead ? k + 1u : 0u, f.accepted ? 1u : 0u, 0u},
-                   s_part, incl, excl, total);
-        if (threadIdx.x == 0) a.partial[blk] = total;
+// The mode of the gather steps (framesum_coalesce_dev.h): slot k is the frame the k-th sort key
+// names, a change of the keys' flow opens a flow, and the flows are recorded beside the runs.
+struct ByFlow {
+    using Part = FlowPart;
+    using Key = uint64_t;  // the slot's sort key
+    static constexpr uint32_t kFlowBit = flows::kFlowHead;
+    static __device__ __forceinline__ Key key(const FlArgs& a, uint32_t k) { return a.sorted[k]; }
+    static __device__ __forceinline__ Key shfl_up_key(Key sk) { return shfl_up_u64(sk, 1); }
+    static __device__ __forceinline__ uint32_t frame(const FlArgs& a, uint32_t, Key sk) { return flows::sort_index(sk, a.b); }
+    // the accepted frames come first, so an accepted slot behind slot 0 follows an accepted one
+    static __device__ __forceinline__ bool flow_head(const FlArgs& a, uint32_t k, bool acc, bool pacc, Key sk, Key psk) {
+        return acc && (k == 0 || !pacc || flows::sort_rep(psk, a.b) != flows::sort_rep(sk, a.b));
     }
-}
-
-// One workgroup: prefix[b] = the partials of the workgroups before b; the totals.
-__global__ void __launch_bounds__(kThreads) flows_scan_partials(const FlArgs a) {
-    __shared__ FlowPart s_part[kWaves];
-    FlowPart carry = FlowPart{};
-    for (uint32_t base = 0; base < a.n_blocks; base += kScanBlock) {
-        const uint32_t b = base + threadIdx.x;
-        FlowPart incl, excl, total;
-        block_scan(b < a.n_blocks ? a.partial[b] : FlowPart{}, s_part, incl, excl, total);
-        if (b < a.n_blocks) a.prefix[b] = combine(carry, excl);
-        carry = combine(carry, total);
+    static __device__ __forceinline__ Part part(uint64_t len, bool head, bool fhead, bool acc, uint32_t k) {
+        return Part{len, head ? 1u : 0u, head ? k + 1u : 0u, fhead ? 1u : 0u, fhead ? k + 1u : 0u, acc ? 1u : 0u, 0u};
     }
-    if (threadIdx.x == 0) {
+    static __device__ __forceinline__ void write_totals(const FlArgs& a, const Part& carry) {
         fs_rx_flow_totals t;
         t.payload_bytes = carry.sum;
         t.n_runs = carry.heads;
@@ -267,94 +233,34 @@ __global__ void __launch_bounds__(kThreads) flows_scan_partials(const FlArgs a) 
         t.n_accepted = carry.acc;
         t.reserved = 0;
         *a.totals = t;
-        *a.copied = carry.sum <= a.cap ? carry.sum : 0ull;
     }
-}
+    static __device__ __forceinline__ void apply_extra(const FlArgs& a, uint32_t k, uint32_t i, const Part& in, bool acc) {
+        a.flowidx[k] = acc ? in.fheads - 1u : kNoRun;
+        a.fhidx[k] = acc ? in.fidx1 - 1u : kNoRun;
+        if (acc) a.order[k] = i;  // (slot k of an accepted frame is below n_accepted)
+    }
+    // the flow ends where the next slot opens another, or holds no accepted frame: its last slot
+    // writes the record, behind its copy
+    static __device__ __forceinline__ void flow_record(const FlArgs& a, uint32_t k, uint32_t ny, uint64_t off, uint32_t len) {
+        if (!a.flows || ((ny & kAccepted) && !(ny & flows::kFlowHead))) return;
+        const uint32_t fh = a.fhidx[k];
+        const uint64_t foff = a.payoff[fh];
+        const uint32_t r0 = a.runidx[fh];
+        fs_rx_flow fl;
+        fl.payload_off = foff;
+        fl.payload_len = off + len - foff;
+        fl.first_run = r0;
+        fl.n_runs = a.runidx[k] - r0 + 1u;
+        fl.first_frame = fh;
+        fl.n_frames = k - fh + 1u;
+        a.flows[a.flowidx[k]] = fl;
+    }
+};
 
-__global__ void __launch_bounds__(kThreads) flows_apply(const FlArgs a) {
-    __shared__ FlowPart s_part[kWaves];
-    for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
-        const uint32_t k = blk * kScanBlock + threadIdx.x;
-        const uint2 r = k < a.n ? a.rec[k] : make_uint2(0u, 0u);
-        const bool acc = (r.y & kAccepted) != 0, head = (r.y & kHead) != 0, fhead = (r.y & flows::kFlowHead) != 0;
-        const uint32_t len = acc ? rec_len(r.x) : 0u;
-        FlowPart incl, excl, total;
-        block_scan(FlowPart{(uint64_t)len, head ? 1u : 0u, head ? k + 1u : 0u, fhead ? 1u : 0u, fhead ? k + 1u : 0u,
-                            acc ? 1u : 0u, 0u},
-                   s_part, incl, excl, total);
-        const FlowPart base = a.prefix[blk];
-        const FlowPart in = combine(base, incl);
-        const uint64_t off = base.sum + excl.sum;
-        if (k < a.n) {
-            const uint32_t i = flows::sort_index(a.sorted[k], a.b);
-            const uint32_t run = acc ? in.heads - 1u : kNoRun;
-            a.payoff[k] = off;
-            a.runidx[k] = run;
-            a.hidx[k] = acc ? in.hidx1 - 1u : kNoRun;
-            a.flowidx[k] = acc ? in.fheads - 1u : kNoRun;
-            a.fhidx[k] = acc ? in.fidx1 - 1u : kNoRun;
-            if (acc) a.order[k] = i;  // (slot k of an accepted frame is below n_accepted)
-            if (a.run_of && i < a.n) a.run_of[i] = run;
-        }
-        // how far the packed buffer gets written when payload_cap cuts it short: as coalesce_apply
-        if (a.totals->payload_bytes > a.cap) {
-            unsigned long long end = (acc && off + len <= a.cap) ? off + len : 0ull;
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) {
-                const uint32_t lo = __shfl_xor((uint32_t)end, m, 64), hi = __shfl_xor((uint32_t)(end >> 32), m, 64);
-                const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-                end = o > end ? o : end;
-            }
-            if ((threadIdx.x & 63u) == 0 && end != 0ull) atomicMax(a.copied, end);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(kThreads) flows_copy(const FlArgs a) {
-    const uint32_t sub = threadIdx.x & (kGroup - 1u), grp = threadIdx.x / kGroup;
-    const uint32_t n_tiles = (a.n + kTileFrames - 1u) / kTileFrames;
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint32_t k = tile * kTileFrames + grp;
-        if (k >= a.n) continue;
-        const uint2 r = a.rec[k];
-        if (!(r.y & kAccepted)) continue;
-        const uint64_t off = a.payoff[k];
-        const uint32_t i = flows::sort_index(a.sorted[k], a.b);
-        const uint64_t at = a.offsets[i];
-        const uint32_t len = rec_len(r.x);
-        if (len != 0 && off + len <= a.cap) copy_payload(a.payload + off, a.frames + at + rec_start(r.x), len, sub);
-        if (sub == 8 || sub == 9) {
-            const uint32_t ny = k + 1u == a.n ? 0u : a.rec[k + 1u].y;
-            if (sub == 8 && (ny & (kAccepted | kHead)) != kAccepted) {
-                // the run ends here: the next slot does not continue it
-                const uint32_t hd = a.hidx[k];
-                const uint64_t hoff = a.payoff[hd];
-                fs_rx_run run;
-                run.payload_off = hoff;
-                run.payload_len = (uint32_t)(off + len - hoff);
-                run.first_frame = hd;
-                run.n_frames = k - hd + 1u;
-                run.tcp_flags = (uint8_t)run_flags(rec_flags(a.rec[hd].x), rec_flags(r.x));
-                run.reserved[0] = run.reserved[1] = run.reserved[2] = 0;
-                a.runs[a.runidx[k]] = run;
-            }
-            if (sub == 9 && a.flows && (!(ny & kAccepted) || (ny & flows::kFlowHead))) {
-                // the flow ends here: the next slot opens another, or holds no accepted frame
-                const uint32_t fh = a.fhidx[k];
-                const uint64_t foff = a.payoff[fh];
-                const uint32_t r0 = a.runidx[fh];
-                fs_rx_flow fl;
-                fl.payload_off = foff;
-                fl.payload_len = off + len - foff;
-                fl.first_run = r0;
-                fl.n_runs = a.runidx[k] - r0 + 1u;
-                fl.first_frame = fh;
-                fl.n_frames = k - fh + 1u;
-                a.flows[a.flowidx[k]] = fl;
-            }
-        }
-    }
-}
+__global__ void __launch_bounds__(kThreads) flows_classify(const FlArgs a) { gather_classify<ByFlow>(a); }
+__global__ void __launch_bounds__(kThreads) flows_scan_partials(const FlArgs a) { gather_scan_partials<ByFlow>(a); }
+__global__ void __launch_bounds__(kThreads) flows_apply(const FlArgs a) { gather_apply<ByFlow>(a); }
+__global__ void __launch_bounds__(kThreads) flows_copy(const FlArgs a) { gather_copy<ByFlow>(a); }
 
 hipError_t sort_keys(void* temp, size_t& temp_bytes, uint64_t* in, uint64_t* out, uint32_t n, uint32_t bits,
                      hipStream_t stream) {
@@ -365,7 +271,6 @@ hipError_t sort_keys(void* temp, size_t& temp_bytes, uint64_t* in, uint64_t* out
 
 FlowScratch flows_scratch(uint32_t n) {
     FlowScratch s;
-    const uint64_t nb = ((uint64_t)n + kScanBlock - 1) / kScanBlock;
     const uint64_t slots = flows::table_slots(n);
     size_t sort_bytes = 0;
     // (a null pointer: the sort only reports what it needs)
@@ -375,16 +280,11 @@ FlowScratch flows_scratch(uint32_t n) {
     s.keys = at, at += 16ull * n;
     s.sk_in = at, at += 8ull * n;
     s.sorted = at, at += 8ull * n;
-    s.rec = at, at += 8ull * n;
-    s.payoff = at, at += 8ull * n;
-    s.partial = at, at += 32ull * nb;
-    s.prefix = at, at += 32ull * nb;
-    s.copied = at, at += 8;
+    at = lay_scan_arrays(s, at, n, sizeof(FlowPart));
     s.table = at, at += 4ull * slots;  // table and rep lie together: one memset covers both
     s.rep = at, at += 4ull * slots;
     s.slot_of = at, at += 4ull * n;
-    s.runidx = at, at += 4ull * n;
-    s.hidx = at, at += 4ull * n;
+    at = lay_run_arrays(s, at, n);
     s.flowidx = at, at += 4ull * n;
     s.fhidx = at, at += 4ull * n;
     at = (at + 255u) & ~255ull;
@@ -400,48 +300,29 @@ hipError_t launch_coalesce_flows(const uint8_t* frames, const uint64_t* offsets,
                                  fs_rx_flow_totals* totals, uint8_t* scratch, const FlowScratch& s, uint32_t hash_mask,
                                  int max_workgroups, uint32_t steps, hipStream_t stream) {
     FlArgs a;
-    a.frames = frames;
-    a.offsets = offsets;
-    a.lengths = lengths;
-    a.status = status;
+    const GatherGrids g = fill_gather_args(a, frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, run_of,
+                                           scratch, s, max_workgroups);
     a.keys = reinterpret_cast<uint4*>(scratch + s.keys);
     a.table = reinterpret_cast<uint32_t*>(scratch + s.table);
     a.rep = reinterpret_cast<uint32_t*>(scratch + s.rep);
     a.slot_of = reinterpret_cast<uint32_t*>(scratch + s.slot_of);
     a.sk_in = reinterpret_cast<uint64_t*>(scratch + s.sk_in);
     a.sorted = reinterpret_cast<uint64_t*>(scratch + s.sorted);
-    a.rec = reinterpret_cast<uint2*>(scratch + s.rec);
-    a.payoff = reinterpret_cast<uint64_t*>(scratch + s.payoff);
-    a.runidx = reinterpret_cast<uint32_t*>(scratch + s.runidx);
-    a.hidx = reinterpret_cast<uint32_t*>(scratch + s.hidx);
     a.flowidx = reinterpret_cast<uint32_t*>(scratch + s.flowidx);
     a.fhidx = reinterpret_cast<uint32_t*>(scratch + s.fhidx);
-    a.partial = reinterpret_cast<FlowPart*>(scratch + s.partial);
-    a.prefix = reinterpret_cast<FlowPart*>(scratch + s.prefix);
-    a.copied = reinterpret_cast<unsigned long long*>(scratch + s.copied);
-    a.payload = payload;
-    a.cap = payload_cap;
-    a.runs = runs;
     a.flows = flows_out;
     a.order = order;
-    a.run_of = run_of;
     a.totals = totals;
-    a.n = n;
-    a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
-    a.fcs = (flags & FS_RX_FCS) ? 4u : 0u;
     a.tmask = flows::table_slots(n) - 1u;
     a.hash_mask = hash_mask;
     a.b = flows::index_bits(n);
-    const uint32_t cap = (uint32_t)(max_workgroups > 0 ? max_workgroups : 1);
-    const uint32_t n_tiles = (uint32_t)(((uint64_t)n + kTileFrames - 1) / kTileFrames);
-    const uint32_t g_scan = a.n_blocks < cap ? a.n_blocks : cap, g_copy = n_tiles < cap ? n_tiles : cap;
     hipError_t e = hipSuccess;
     if (steps & kFlowStepOrder) {
-        hipLaunchKernelGGL(flows_keys, dim3(g_scan), dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(flows_keys, dim3(g.scan), dim3(kThreads), 0, stream, a);
         e = hipMemsetAsync(scratch + s.table, 0xFF, 8ull * ((uint64_t)a.tmask + 1u), stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(flows_insert, dim3(g_scan), dim3(kThreads), 0, stream, a);
-        hipLaunchKernelGGL(flows_sortkeys, dim3(g_scan), dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(flows_insert, dim3(g.scan), dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(flows_sortkeys, dim3(g.scan), dim3(kThreads), 0, stream, a);
     }
     if (steps & kFlowStepSort) {
         size_t sort_bytes = s.sort_bytes;
@@ -449,10 +330,10 @@ hipError_t launch_coalesce_flows(const uint8_t* frames, const uint64_t* offsets,
         if (e != hipSuccess) return e;
     }
     if (steps & kFlowStepGather) {
-        hipLaunchKernelGGL(flows_classify, dim3(g_scan), dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(flows_classify, dim3(g.scan), dim3(kThreads), 0, stream, a);
         hipLaunchKernelGGL(flows_scan_partials, dim3(1), dim3(kThreads), 0, stream, a);
-        hipLaunchKernelGGL(flows_apply, dim3(g_scan), dim3(kThreads), 0, stream, a);
-        hipLaunchKernelGGL(flows_copy, dim3(g_copy), dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(flows_apply, dim3(g.scan), dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(flows_copy, dim3(g.copy), dim3(kThreads), 0, stream, a);
     }
     return hipGetLastError();
 }

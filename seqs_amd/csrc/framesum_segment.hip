@@ -21,6 +21,7 @@
 // nothing read back.
 #include <hip/hip_runtime.h>
 
+#include "framesum_coalesce_dev.h"
 #include "framesum_internal.h"
 #include "framesum_segment.h"
 
@@ -50,6 +51,9 @@ void build_segment_tables(SegTables* t) {
 
 namespace {
 
+using codev::load_at;  // 16 bytes, and loads and stores, at any alignment
+using codev::Piece;
+using codev::store_at;
 using segment::SendRec;
 
 // 12 waves per workgroup, two workgroups per CU: the tables (68 KB) fit a CU's LDS twice and the
@@ -83,20 +87,6 @@ __device__ __forceinline__ uint32_t prand16(uint32_t x) {
     return x;
 }
 
-struct __attribute__((packed)) Piece {  // 16 bytes at any alignment
-    uint32_t d[4];
-};
-
-template <typename T>
-__device__ __forceinline__ T load_at(const uint8_t* p) {  // any alignment
-    T v;
-    __builtin_memcpy(&v, p, sizeof v);
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ void store_at(uint8_t* p, T v) {
-    __builtin_memcpy(p, &v, sizeof v);
-}
 // bytes [at, at + 8) of the 16-byte value (lo, hi), for at = 0 or at + width <= 8 or at >= 8
 __device__ __forceinline__ uint64_t bytes_at(uint64_t lo, uint64_t hi, int at) {
     return at < 8 ? lo >> (8 * at) : hi >> (8 * (at - 8));
