@@ -64,6 +64,32 @@ FLOW_DTYPE = np.dtype([("payload_off", "<u8"), ("payload_len", "<u8"), ("first_r
                        ("first_frame", "<u4"), ("n_frames", "<u4")])
 FLOW_TOTALS_DTYPE = np.dtype([("payload_bytes", "<u8"), ("n_runs", "<u4"), ("n_flows", "<u4"), ("n_accepted", "<u4"),
                               ("reserved", "<u4")])
+# fs_rx_sock: one socket of the in-order delivery (48 bytes, no padding), and fs_rx_sock_out (32 bytes)
+SOCK_DTYPE = np.dtype([("key", "u1", (13,)), ("reserved", "u1", (3,)), ("rcv_nxt", "<u4"), ("rcv_wnd", "<u4"),
+                       ("snd_nxt", "<u4"), ("ring_size", "<u4"), ("ring_off", "<u8"), ("ring_wpos", "<u4"),
+                       ("ring_free", "<u4")])
+SOCK_OUT_DTYPE = np.dtype([("rcv_nxt", "<u4"), ("ring_wpos", "<u4"), ("ring_free", "<u4"), ("bytes", "<u4"),
+                           ("n_delivered", "<u4"), ("n_dropped", "<u4"), ("flow", "<u4"), ("stop", "<u4")])
+DELIVER_MAX_SOCKS = 65536
+NO_FLOW = 0xFFFFFFFF  # fs_rx_sock_out.flow / .stop of a socket without a flow in the batch
+
+
+def sock_key(remote_ip, remote_port: int, local_ip, local_port: int) -> np.ndarray:
+    """The 13-byte key of a TCP socket as its received frames carry it (fs_rx_sock.key): protocol 6,
+    source = remote address, destination = local address, source = remote port, destination = local
+    port. An address is 4 bytes, a dotted string or an integer."""
+    def addr(a) -> bytes:
+        if isinstance(a, str):
+            a = bytes(int(x) for x in a.split("."))
+        elif isinstance(a, int):
+            a = a.to_bytes(4, "big")
+        a = bytes(a)
+        assert len(a) == 4, "an IPv4 address is 4 bytes"
+        return a
+
+    key = bytes([6]) + addr(remote_ip) + addr(local_ip) + int(remote_port).to_bytes(2, "big") + \
+        int(local_port).to_bytes(2, "big")
+    return np.frombuffer(key, dtype=np.uint8).copy()
 
 
 class FramesumError(RuntimeError):
@@ -110,6 +136,15 @@ PROTOTYPES = {
 }
 EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
+# The functions include/framesum_deliver.h declares (the second header), in its order. Product
+# symbols like the ones above: a library that lacks one raises in load_library.
+DELIVER_PROTOTYPES = {
+    "fs_deliver_flows_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _u64, _p, _p, _p,
+                                     _p, _p, _p, _p, _p]),
+    "fs_deliver_flows_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _u64, _p,
+                                          _p, _p, _p, _p, _p, _p]),
+}
+
 # Not in the header, set only where the loaded library has them: the test library's hooks
 # (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
 OPTIONAL_PROTOTYPES = {
@@ -145,7 +180,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     if not os.path.exists(p):
         raise FramesumError(f"{p} is missing — run __graft_entry__.build() (or make -C seqs_amd/csrc)")
     lib = ctypes.CDLL(p)
-    for name, (restype, argtypes) in {**PROTOTYPES, **OPTIONAL_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **DELIVER_PROTOTYPES, **OPTIONAL_PROTOTYPES}.items():
         if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)  # (a missing product symbol raises here)

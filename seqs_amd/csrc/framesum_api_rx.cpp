@@ -1,12 +1,16 @@
 // framesum C ABI (include/framesum.h) -- the two RX coalesce families: fs_coalesce_batch and
 // fs_coalesce_batch_host (kernels: framesum_coalesce.hip), fs_coalesce_flows_batch and
-// fs_coalesce_flows_batch_host (framesum_flows.hip), and what their host forms share.
+// fs_coalesce_flows_batch_host (framesum_flows.hip), and what their host forms share -- and
+// (include/framesum_deliver.h) the delivery into socket rings behind the second family:
+// fs_deliver_flows_batch and fs_deliver_flows_batch_host (framesum_deliver.hip).
 #include <algorithm>
 #include <array>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "framesum_ctx.h"
+#include "framesum_deliver.h"
 #include "framesum_flows.h"
 
 using namespace framesum::host;
@@ -180,13 +184,15 @@ static fs_status flows_check(fs_ctx* ctx, const char* fn, const void* frames, co
 }
 
 // The digest launch and the flow coalesce launches of a checked, non-empty device-resident batch on
-// `stream`. `d_copied`: as coalesce_enqueue's.
+// `stream`. `d_copied`: as coalesce_enqueue's. `layout` (nullable): where in the context's scratch the
+// launches leave their per-slot arrays, for the delivery launches behind them.
 static fs_status flows_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
                                uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
                                fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
                                fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, hipStream_t stream,
-                               const uint8_t** d_copied = nullptr) {
+                               const uint8_t** d_copied = nullptr, framesum::FlowScratch* layout = nullptr) {
     const framesum::FlowScratch s = framesum::flows_scratch(n);
+    if (layout) *layout = s;
     if (s.sort_bytes == 0) return set_err(ctx, FS_E_HIP, "fs_coalesce_flows_batch: the sort reports no temporary storage size");
     fs_status st = ctx->fl_scratch.grow(ctx, s.bytes);
     if (st == FS_SUCCESS) st = spare_results(ctx, n, out, status);
@@ -248,5 +254,137 @@ fs_status fs_coalesce_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint6
             return std::array<D2H, 3>{{{flows, d_rest, (uint64_t)t.n_flows * sizeof(fs_rx_flow)},
                                        {order, d_rest + at_order, (uint64_t)t.n_accepted * 4},
                                        {run_of, d_rest + at_run_of, (uint64_t)n * 4}}};
+        });
+}
+
+// ---- In-order TCP delivery (fs_deliver_flows_batch / fs_deliver_flows_batch_host, include/framesum_deliver.h) ----
+
+namespace dl = framesum::deliver;
+
+// Every check of a delivery call: the flow call's, then the socket list's (framesum_deliver.h), which
+// also builds the socket table `table` and gives the span of `rings` the listed rings cover.
+static fs_status deliver_check(fs_ctx* ctx, const char* fn, const void* frames, const void* offsets, const void* lengths,
+                               uint32_t n, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks, const void* rings,
+                               uint64_t rings_bytes, const void* socks_out, const void* payload, uint64_t payload_cap,
+                               const void* runs, const void* order, const void* totals, bool aligned,
+                               std::vector<uint32_t>& table, dl::Check& c) {
+    const fs_status st =
+        flows_check(ctx, fn, frames, offsets, lengths, n, flags, payload, payload_cap, runs, order, totals, aligned);
+    if (st != FS_SUCCESS) return st;
+    c = dl::check_socks(socks, n_socks, rings != nullptr, socks_out != nullptr, rings_bytes, ctx->flow_hash_mask, table);
+    if (c.bad != dl::kGood)
+        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": socket " + std::to_string(c.sock) + ": " + dl::bad_text(c.bad));
+    return FS_SUCCESS;
+}
+
+// The launches of a checked device-resident delivery call on `stream`: the flow call's (or its zero
+// totals for an empty batch), `delivered` zeroed, the socket block staged in a block of its own, the
+// delivery kernels. `d_copied`: as coalesce_enqueue's (non-empty batches only).
+static fs_status deliver_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                                 uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
+                                 const std::vector<uint32_t>& table, uint8_t* rings, fs_rx_sock_out* socks_out,
+                                 uint8_t* delivered, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
+                                 fs_rx_flow* flows, uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals,
+                                 fs_digest* out, uint8_t* status, hipStream_t stream, const uint8_t** d_copied = nullptr) {
+    framesum::FlowScratch fs{};
+    if (n == 0) {
+        FS_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(fs_rx_flow_totals), stream));
+    } else {
+        const fs_status st = flows_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, payload, payload_cap, runs, flows,
+                                           order, run_of, totals, out, status, stream, d_copied, &fs);
+        if (st != FS_SUCCESS) return st;
+        if (delivered) FS_HIP(ctx, hipMemsetAsync(delivered, 0, n, stream));
+    }
+    if (n_socks == 0) return FS_SUCCESS;
+    const dl::Block b = dl::block_of(n_socks);
+    const framesum::DeliverScratch ds = framesum::deliver_scratch(n, n_socks);
+    fs_status st = ctx->dl_scratch.grow(ctx, ds.bytes);
+    if (st != FS_SUCCESS) return st;
+    SegStage* sg = nullptr;
+    st = stage_block(ctx, b.bytes, &sg);
+    if (st != FS_SUCCESS) return st;
+    std::memcpy(sg->h, socks, b.table);
+    std::memcpy(sg->h + b.table, table.data(), 4ull * table.size());
+    FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, b.bytes, hipMemcpyHostToDevice, stream));
+    sg->used = true;  // (from here on the block may be read by queued work)
+    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
+    const hipError_t le = framesum::launch_deliver(frames, offsets, n, ctx->fl_scratch.p, fs, totals, sg->d, n_socks,
+                                                   ctx->flow_hash_mask, rings, socks_out, delivered, ctx->dl_scratch.p, ds,
+                                                   wgs, stream);
+    const hipError_t re = hipEventRecord(sg->done, stream);
+    if (le != hipSuccess) return hip_err(ctx, le, "fs_deliver_flows_batch: launch");
+    if (re != hipSuccess) return hip_err(ctx, re, "hipEventRecord(sg->done, stream)");
+    return FS_SUCCESS;
+}
+
+fs_status fs_deliver_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                                 uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
+                                 uint8_t* rings, uint64_t rings_bytes, fs_rx_sock_out* socks_out, uint8_t* delivered,
+                                 uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows,
+                                 uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out,
+                                 uint8_t* status, void* stream) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    std::vector<uint32_t> table;
+    dl::Check c;
+    const fs_status st = deliver_check(ctx, "fs_deliver_flows_batch", frames, offsets, lengths, n, flags, socks, n_socks, rings,
+                                       rings_bytes, socks_out, payload, payload_cap, runs, order, totals, true, table, c);
+    if (st != FS_SUCCESS) return st;
+    FS_HIP(ctx, hipSetDevice(ctx->device));
+    return deliver_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, socks, n_socks, table, rings, socks_out, delivered,
+                           payload, payload_cap, runs, flows, order, run_of, totals, out, status,
+                           reinterpret_cast<hipStream_t>(stream));
+}
+
+fs_status fs_deliver_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                                      const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags,
+                                      const fs_rx_sock* socks, uint32_t n_socks, uint8_t* rings, uint64_t rings_bytes,
+                                      fs_rx_sock_out* socks_out, uint8_t* delivered, uint8_t* payload,
+                                      uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order,
+                                      uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    const char* const fn = "fs_deliver_flows_batch_host";
+    std::vector<uint32_t> table;
+    dl::Check c;
+    const fs_status ast = deliver_check(ctx, fn, frames, offsets, lengths, n, flags, socks, n_socks, rings, rings_bytes,
+                                        socks_out, payload, payload_cap, runs, order, totals, false, table, c);
+    if (ast != FS_SUCCESS) return ast;
+    if (n == 0) {  // nothing for a device to do: the sockets keep their state
+        std::memset(totals, 0, sizeof(fs_rx_flow_totals));
+        for (uint32_t s = 0; s < n_socks; ++s) socks_out[s] = dl::untouched(socks[s]);
+        return FS_SUCCESS;
+    }
+    // the device's socks_out and the rings' span (the kernels address ring bytes at base + ring_off)
+    const uint64_t span = c.hi - c.lo;
+    fs_status st = begin_host_call(ctx);
+    if (st == FS_SUCCESS) st = ctx->dl_arrays.grow(ctx, (uint64_t)n_socks * sizeof(fs_rx_sock_out));
+    if (st == FS_SUCCESS) st = ctx->dl_rings.grow(ctx, span);
+    if (st != FS_SUCCESS) return st;
+    fs_rx_sock_out* d_socks_out = ctx->dl_arrays.as<fs_rx_sock_out>();
+    uint8_t* d_rings = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ctx->dl_rings.p) - c.lo);
+    // behind the runs, per frame: a flow (32), order (4), run_of (4), delivered (1)
+    const uint64_t at_order = (uint64_t)n * 32, at_run_of = (uint64_t)n * 36, at_delivered = (uint64_t)n * 40;
+    return rx_host(
+        ctx, fn, frames, frames_bytes, offsets, lengths, n, payload, payload_cap, runs, totals, out, status, ctx->fl_arrays, 41,
+        [&](const Staged& s, uint64_t d_cap, fs_rx_run* d_runs, uint8_t* d_rest, fs_rx_flow_totals* d_totals,
+            const uint8_t** d_copied) {
+            // the span goes in first, so that the copy back returns the caller's own bytes between the rings
+            if (span != 0) FS_HIP(ctx, hipMemcpyAsync(ctx->dl_rings.p, rings + c.lo, span, hipMemcpyHostToDevice, s.ks));
+            return deliver_enqueue(ctx, s.base, s.d_off, s.d_len, n, mtu, flags, socks, n_socks, table, d_rings, d_socks_out,
+                                   delivered ? d_rest + at_delivered : nullptr, ctx->co_payload.p, d_cap, d_runs,
+                                   flows ? reinterpret_cast<fs_rx_flow*>(d_rest) : nullptr,
+                                   reinterpret_cast<uint32_t*>(d_rest + at_order),
+                                   run_of ? reinterpret_cast<uint32_t*>(d_rest + at_run_of) : nullptr, d_totals, s.d_out,
+                                   s.d_st, s.ks, d_copied);
+        },
+        [&](const fs_rx_flow_totals& t) { return t.n_accepted <= n && t.n_runs <= t.n_accepted && t.n_flows <= t.n_runs; },
+        [&](const fs_rx_flow_totals& t, const uint8_t* d_rest) {
+            return std::array<D2H, 6>{{{flows, d_rest, (uint64_t)t.n_flows * sizeof(fs_rx_flow)},
+                                       {order, d_rest + at_order, (uint64_t)t.n_accepted * 4},
+                                       {run_of, d_rest + at_run_of, (uint64_t)n * 4},
+                                       {delivered, d_rest + at_delivered, (uint64_t)n},
+                                       {n_socks ? rings + c.lo : nullptr, ctx->dl_rings.p, span},
+                                       {socks_out, d_socks_out, (uint64_t)n_socks * sizeof(fs_rx_sock_out)}}};
         });
 }

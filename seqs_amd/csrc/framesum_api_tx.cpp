@@ -23,7 +23,7 @@ static fs_status segment_check(fs_ctx* ctx, const char* fn, const fs_tx_send* se
 }
 
 // A staging block of at least `bytes` bytes whose previous kernel has ended.
-static fs_status segment_stage_block(fs_ctx* ctx, uint64_t bytes, SegStage** out) {
+fs_status framesum::host::stage_block(fs_ctx* ctx, uint64_t bytes, SegStage** out) {
     SegStage* pick = nullptr;
     for (SegStage& sg : ctx->seg_stage) {
         if (sg.used) {
@@ -51,7 +51,7 @@ static fs_status segment_stage_block(fs_ctx* ctx, uint64_t bytes, SegStage** out
         const uint64_t cap = (bytes + 4095) & ~4095ull;
         if (hipHostMalloc(reinterpret_cast<void**>(&pick->h), cap, hipHostMallocDefault) != hipSuccess ||
             hipMalloc(&pick->d, cap) != hipSuccess)
-            return set_err(ctx, FS_E_NOMEM, "fs_segment_batch: staging allocation failed");
+            return set_err(ctx, FS_E_NOMEM, "staging block allocation failed");
         pick->cap = cap;
     }
     *out = pick;
@@ -79,7 +79,7 @@ static fs_status segment_enqueue(fs_ctx* ctx, const fs_tx_send* sends, uint32_t 
     }
     const seg::Block b = seg::block_of(n_sends, L.id_entries);
     SegStage* sg = nullptr;
-    const fs_status st = segment_stage_block(ctx, b.bytes, &sg);
+    const fs_status st = stage_block(ctx, b.bytes, &sg);
     if (st != FS_SUCCESS) return st;
     seg::stage(sends, n_sends, flags, align, b, sg->h);
     FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, b.bytes, hipMemcpyHostToDevice, stream));

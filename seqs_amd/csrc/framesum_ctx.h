@@ -105,6 +105,10 @@ struct fs_ctx {
     DevBuf fl_scratch, fl_arrays;
     uint32_t flow_hash_mask = 0xFFFFFFFFu;
     uint32_t flow_steps = framesum::kFlowStepsAll;
+    // in-order TCP delivery: the kernels' scratch, and the device buffers of
+    // fs_deliver_flows_batch_host (the rings' span; socks_out). Its socket block is staged through
+    // seg_stage, like the sends of fs_segment_batch.
+    DevBuf dl_scratch, dl_rings, dl_arrays;
     std::string err;
 };
 
@@ -143,6 +147,11 @@ void drain_host_streams(fs_ctx* ctx);
             return framesum::host::hip_err(ctx, e_, #call); \
         }                                                \
     } while (0)
+
+// A staging block (fs_ctx::seg_stage) of at least `bytes` bytes whose previous kernel has ended; the
+// caller fills `h`, copies it to `d`, sets `used` and records `done` behind its last reader.
+// framesum_api_tx.cpp.
+fs_status stage_block(fs_ctx* ctx, uint64_t bytes, SegStage** out);
 
 // One launch of the context's kernel choice.
 // `force` < 0: the context's kernel choice (fs_ctx_set_kernel).

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/framesum.h"
+#include "../../include/framesum_deliver.h"
 #include "framesum_choice.h"
 
 namespace framesum {
@@ -118,5 +119,20 @@ hipError_t launch_coalesce_flows(const uint8_t* frames, const uint64_t* offsets,
                                  fs_rx_run* runs, fs_rx_flow* flows_out, uint32_t* order, uint32_t* run_of,
                                  fs_rx_flow_totals* totals, uint8_t* scratch, const FlowScratch& s, uint32_t hash_mask,
                                  int max_workgroups, uint32_t steps, hipStream_t stream);
+
+// ---- In-order TCP delivery (framesum_deliver.hip). The launches that follow a batch's flow launches
+// on `stream` (fs_deliver_flows_batch in include/framesum_deliver.h) and read what those left in
+// `flow_scratch` (laid out as `fs`) and in `totals`. `d_block`: the device copy of the staged block
+// (framesum_deliver.h block_of: the socket records, then the socket table). `scratch`:
+// deliver_scratch(n, n_socks).bytes of device memory, 8-byte aligned. With n of 0 only the sockets'
+// out records are written. `max_workgroups` caps every grid.
+struct DeliverScratch {
+    uint64_t mk, dwpos, sock_first, flow_sock, bytes;
+};
+DeliverScratch deliver_scratch(uint32_t n, uint32_t n_socks);
+hipError_t launch_deliver(const uint8_t* frames, const uint64_t* offsets, uint32_t n, const uint8_t* flow_scratch,
+                          const FlowScratch& fs, const fs_rx_flow_totals* totals, const uint8_t* d_block, uint32_t n_socks,
+                          uint32_t hash_mask, uint8_t* rings, fs_rx_sock_out* socks_out, uint8_t* delivered,
+                          uint8_t* scratch, const DeliverScratch& s, int max_workgroups, hipStream_t stream);
 
 }  // namespace framesum

@@ -21,9 +21,10 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .abi import (  # noqa: F401 (re-exported: this module is the binding's public face)
-    DIGEST_DTYPE, EXPORTED_SYMBOLS, FCS_APPEND, FILL_CSUM, FLOW_DTYPE, FLOW_TOTALS_DTYPE, FS_E_HIP, FS_E_INVALID,
-    FS_E_NODEVICE, FS_E_NOMEM, FS_ERR_FCS, FS_SUCCESS, NO_RUN, PROTOTYPES, RUN_DTYPE, RX_FCS, SEGMENT_MAX_FRAMES,
-    SEND_DTYPE, TEST_LIB_PATH, TOTALS_DTYPE, VERDICTS, FramesumError, lib_path, load_library,
+    DELIVER_MAX_SOCKS, DELIVER_PROTOTYPES, DIGEST_DTYPE, EXPORTED_SYMBOLS, FCS_APPEND, FILL_CSUM, FLOW_DTYPE,
+    FLOW_TOTALS_DTYPE, FS_E_HIP, FS_E_INVALID, FS_E_NODEVICE, FS_E_NOMEM, FS_ERR_FCS, FS_SUCCESS, NO_FLOW, NO_RUN,
+    PROTOTYPES, RUN_DTYPE, RX_FCS, SEGMENT_MAX_FRAMES, SEND_DTYPE, SOCK_DTYPE, SOCK_OUT_DTYPE, TEST_LIB_PATH,
+    TOTALS_DTYPE, VERDICTS, FramesumError, lib_path, load_library, sock_key,
 )
 
 _vp, _u64 = ctypes.c_void_p, ctypes.c_uint64
@@ -72,11 +73,13 @@ def _host_head(frames, offsets, lengths, n):
     return _array_ptr(frames), frames.nbytes, _array_ptr(offsets), _array_ptr(lengths), n
 
 
-# The two RX coalesce calls: (the device form's C function, the host form adds "_host"; the totals
-# record; the arrays between `runs` and `run_of`, each with the totals field that counts its entries).
+# The RX calls: (the device form's C function, the host form adds "_host"; the totals record; the
+# arrays between `runs` and `run_of`, each with the totals field that counts its entries). The
+# delivery call is the flow call with its socket arguments between `flags` and `payload`.
 _RX = ("fs_coalesce_batch", TOTALS_DTYPE, ())
 _RX_FLOWS = ("fs_coalesce_flows_batch", FLOW_TOTALS_DTYPE,
              ((FLOW_DTYPE, "n_flows"), (np.dtype(np.uint32), "n_accepted")))
+_RX_DELIVER = ("fs_deliver_flows_batch", *_RX_FLOWS[1:])
 
 
 @dataclass
@@ -342,8 +345,10 @@ class Engine(_Handle):
         return res
 
     # ---- RX coalesce (plain: _RX, flow-aware: _RX_FLOWS) ----------------------
-    def _rx_device(self, rx, frames, offsets, lengths, mtu, flags, payload, stream):
-        """(payload, runs, *the call's further record tensors, run_of, totals, out, status)."""
+    def _rx_device(self, rx, frames, offsets, lengths, mtu, flags, payload, stream, socks=()):
+        """(payload, runs, *the call's further record tensors, run_of, totals, out, status). `socks`:
+        the delivery call's arguments between `flags` and `payload`; only that call takes `payload`
+        False (no packed copy: a null pointer and a cap of 0, and None comes back)."""
         import torch
 
         name, totals_dtype, between = rx
@@ -351,34 +356,43 @@ class Engine(_Handle):
         out, status = _result_tensors(n, dev, None, None)
         if payload is None:
             payload = torch.empty((frames.numel(),), dtype=torch.uint8, device=dev)
-        assert payload.is_cuda and payload.dtype == torch.uint8 and payload.is_contiguous()
+        if payload is False:
+            payload_args = (None, 0)
+        else:
+            assert payload.is_cuda and payload.dtype == torch.uint8 and payload.is_contiguous()
+            payload_args = (_tensor_ptr(payload), payload.numel())
         # a record array is (n, record bytes) uint8, a uint32 array int32 (-1 = NO_RUN)
         records = [torch.empty((n, d.itemsize), dtype=torch.uint8, device=dev) if d.fields else
                    torch.empty((n,), dtype=torch.int32, device=dev)
                    for d in (RUN_DTYPE, *(d for d, _ in between), np.dtype(np.uint32))]
         totals = torch.empty((totals_dtype.itemsize,), dtype=torch.uint8, device=dev)
-        extra = (flags, _tensor_ptr(payload), payload.numel(), *map(_tensor_ptr, records), _tensor_ptr(totals))
+        extra = (flags, *socks, *payload_args, *map(_tensor_ptr, records), _tensor_ptr(totals))
         self._resident(name, frames, offsets, lengths, mtu, extra, out, status, stream)
-        return (payload, *records, totals, out, status)
+        return (None if payload is False else payload, *records, totals, out, status)
 
-    def _rx_host(self, rx, frames, offsets, lengths, mtu, flags, payload):
+    def _rx_host(self, rx, frames, offsets, lengths, mtu, flags, payload, socks=()):
         """_rx_device's tuple as numpy arrays, each record array cut to its written entries and the
         totals as one scalar record."""
         name, totals_dtype, between = rx
         frames, offsets, lengths, n = _host_batch(frames, offsets, lengths)
         if payload is None:
             payload = np.zeros(int(lengths.sum(dtype=np.uint64)), dtype=np.uint8)
-        assert payload.dtype == np.uint8 and payload.flags["C_CONTIGUOUS"] and payload.flags["WRITEABLE"]
+        if payload is False:
+            payload_args = (None, 0)
+        else:
+            assert payload.dtype == np.uint8 and payload.flags["C_CONTIGUOUS"] and payload.flags["WRITEABLE"]
+            payload_args = (_array_ptr(payload), payload.nbytes)
         runs, *more, run_of = [np.zeros(n, dtype=d) for d in (RUN_DTYPE, *(d for d, _ in between), np.uint32)]
         totals = np.zeros(1, dtype=totals_dtype)
         out = np.zeros(n, dtype=DIGEST_DTYPE)
         status = np.zeros(n, dtype=np.uint8)
         st = getattr(self.lib, name + "_host")(
-            self._ctx, *_host_head(frames, offsets, lengths, n), mtu, flags, _array_ptr(payload), payload.nbytes,
+            self._ctx, *_host_head(frames, offsets, lengths, n), mtu, flags, *socks, *payload_args,
             *map(_array_ptr, (runs, *more, run_of, totals, out, status)))
         self._check(st, name + "_host")
         t = totals[0]
-        return (payload, runs[: int(t["n_runs"])], *(a[: int(t[count])] for a, (_, count) in zip(more, between)),
+        return (None if payload is False else payload, runs[: int(t["n_runs"])],
+                *(a[: int(t[count])] for a, (_, count) in zip(more, between)),
                 run_of, t, out, status)
 
     def coalesce_device(self, frames, offsets, lengths, mtu: int = 0, flags: int = 0, payload=None, stream=None):
@@ -450,6 +464,44 @@ class Engine(_Handle):
                         [(int(r["tcp_flags"]),
                           bytes(payload[int(r["payload_off"]) : int(r["payload_off"]) + int(r["payload_len"])])) for r in rs]))
         return res
+
+    # ---- in-order TCP delivery into socket rings (include/framesum_deliver.h) ----
+    def deliver_flows_device(self, frames, offsets, lengths, socks: np.ndarray, rings, mtu: int = 0, flags: int = 0,
+                             payload=None, delivered: bool = True, stream=None):
+        """coalesce_flows_device plus the delivery of every flow that belongs to a listed socket
+        (fs_deliver_flows_batch): `socks` is a SOCK_DTYPE array on the host (key from sock_key(), the
+        receive state, and where in `rings` the socket's ring lies); `rings` a uint8 CUDA tensor. The
+        flow's data segments are admitted in order (Seq == rcv_nxt, inside the window, no ACK of
+        unsent data, room in the ring) and their bytes go from the frames into the ring, wrapping at
+        its end. `payload` False: no packed copy. Returns (socks_out, delivered, payload, runs, flows,
+        order, run_of, totals, out, status) device tensors: socks_out (n_socks, 32) uint8 =
+        SOCK_OUT_DTYPE records, delivered (n,) uint8 (1 admitted, 2 considered and not admitted, 0
+        otherwise; None when `delivered` is False), the rest as coalesce_flows_device gives them.
+        Asynchronous on `stream`; split_socks() brings socks_out to the host."""
+        import torch
+
+        socks = np.ascontiguousarray(socks, dtype=SOCK_DTYPE)
+        n, dev = int(lengths.numel()), frames.device
+        assert rings.is_cuda and rings.dtype == torch.uint8 and rings.is_contiguous()
+        socks_out = torch.empty((int(socks.size), SOCK_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        marks = torch.empty((n,), dtype=torch.uint8, device=dev) if delivered else None
+        args = (_array_ptr(socks), int(socks.size), _tensor_ptr(rings), rings.numel(), _tensor_ptr(socks_out),
+                _tensor_ptr(marks) if delivered else None)
+        return (socks_out, marks, *self._rx_device(_RX_DELIVER, frames, offsets, lengths, mtu, flags, payload, stream, args))
+
+    def deliver_flows_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, socks: np.ndarray,
+                           rings: np.ndarray, mtu: int = 0, flags: int = 0, payload=None, delivered: bool = True):
+        """deliver_flows_device from and to host memory (fs_deliver_flows_batch_host): `rings` is a
+        writable uint8 array, written in place inside the listed rings only. Returns (socks_out
+        SOCK_OUT_DTYPE[n_socks], delivered uint8[n] or None, then coalesce_flows_host's tuple)."""
+        socks = np.ascontiguousarray(socks, dtype=SOCK_DTYPE)
+        assert isinstance(rings, np.ndarray) and rings.dtype == np.uint8 and rings.flags["C_CONTIGUOUS"]
+        assert rings.flags["WRITEABLE"], "deliver_flows_host writes into `rings`"
+        socks_out = np.zeros(int(socks.size), dtype=SOCK_OUT_DTYPE)
+        marks = np.zeros(int(np.asarray(lengths).size), dtype=np.uint8) if delivered else None
+        args = (_array_ptr(socks), int(socks.size), _array_ptr(rings), rings.nbytes, _array_ptr(socks_out),
+                _array_ptr(marks) if delivered else None)
+        return (socks_out, marks, *self._rx_host(_RX_DELIVER, frames, offsets, lengths, mtu, flags, payload, args))
 
     # ---- host-staged path (numpy in, numpy out) -----------------------------
     def host_empty(self, shape, dtype=np.uint8) -> np.ndarray:
@@ -590,6 +642,11 @@ def split_flows(runs, flows, order, totals):
     t = _records(totals, FLOW_TOTALS_DTYPE)[0]
     return (_records(runs[: int(t["n_runs"])], RUN_DTYPE), _records(flows[: int(t["n_flows"])], FLOW_DTYPE),
             _records(order[: int(t["n_accepted"])], np.uint32), t)
+
+
+def split_socks(socks_out) -> np.ndarray:
+    """The host view of deliver_flows_device's `socks_out` tensor (this waits for it): SOCK_OUT_DTYPE[n_socks]."""
+    return _records(socks_out, SOCK_OUT_DTYPE)
 
 
 def shard_count(n: int, nshards: int, shard: int) -> int:
