@@ -72,6 +72,16 @@ SOCK_OUT_DTYPE = np.dtype([("rcv_nxt", "<u4"), ("ring_wpos", "<u4"), ("ring_free
                            ("n_delivered", "<u4"), ("n_dropped", "<u4"), ("flow", "<u4"), ("stop", "<u4")])
 DELIVER_MAX_SOCKS = 65536
 NO_FLOW = 0xFFFFFFFF  # fs_rx_sock_out.flow / .stop of a socket without a flow in the batch
+# fs_tx_sock: one socket of the ring send (104 bytes, no padding), and fs_tx_sock_out (32 bytes)
+TX_SOCK_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("ring_off", "<u8"), ("ring_size", "<u4"),
+                          ("ring_rpos", "<u4"), ("ring_buffered", "<u4"), ("snd_una", "<u4"), ("snd_nxt", "<u4"),
+                          ("snd_wnd", "<u4"), ("rcv_nxt", "<u4"), ("rcv_wnd", "<u4"), ("max_frames", "<u4"),
+                          ("flags", "<u4")])
+TX_SOCK_OUT_DTYPE = np.dtype([("snd_nxt", "<u4"), ("ring_rpos", "<u4"), ("ring_buffered", "<u4"), ("bytes", "<u4"),
+                              ("n_frames", "<u4"), ("first_frame", "<u4"), ("ip_id", "<u4"), ("sent", "<u4")])
+SEND_MAX_SOCKS = 65536
+SEND_NONE = 0xFFFFFFFF  # fs_tx_sock_out.first_frame of a socket that made no frame
+TX_ACK, TX_FIN, TX_PSH = 1, 2, 4  # fs_tx_sock.flags
 
 
 def sock_key(remote_ip, remote_port: int, local_ip, local_port: int) -> np.ndarray:
@@ -145,6 +155,13 @@ DELIVER_PROTOTYPES = {
                                           _p, _p, _p, _p, _p, _p]),
 }
 
+# The functions include/framesum_send.h declares (the third header), in its order: product symbols too.
+SEND_RINGS_PROTOTYPES = {
+    "fs_send_rings_layout": (_st, [_p, _u32, _u32, _u32, _pu64, _pu64, _p]),
+    "fs_send_rings_batch": (_st, [_p, _p, _u32, _p, _u64, _u32, _u32, _u32, _p, _u64, _p, _p, _p, _p, _p, _p]),
+    "fs_send_rings_batch_host": (_st, [_p, _p, _u32, _p, _u64, _u32, _u32, _u32, _p, _u64, _p, _p, _p, _p, _p]),
+}
+
 # Not in the header, set only where the loaded library has them: the test library's hooks
 # (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
 OPTIONAL_PROTOTYPES = {
@@ -180,7 +197,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     if not os.path.exists(p):
         raise FramesumError(f"{p} is missing — run __graft_entry__.build() (or make -C seqs_amd/csrc)")
     lib = ctypes.CDLL(p)
-    for name, (restype, argtypes) in {**PROTOTYPES, **DELIVER_PROTOTYPES, **OPTIONAL_PROTOTYPES}.items():
+    tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **OPTIONAL_PROTOTYPES}
+    for name, (restype, argtypes) in tables.items():
         if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)  # (a missing product symbol raises here)

@@ -58,25 +58,31 @@ fs_status framesum::host::stage_block(fs_ctx* ctx, uint64_t bytes, SegStage** ou
     return FS_SUCCESS;
 }
 
+// The frame-building kernels' table basis on the device, built on the context's first such call.
+fs_status framesum::host::seg_tables(fs_ctx* ctx) {
+    if (ctx->d_seg_tables) return FS_SUCCESS;
+    framesum::SegTables* h = new (std::nothrow) framesum::SegTables;
+    if (!h) return set_err(ctx, FS_E_NOMEM, "frame build: out of host memory");
+    framesum::build_segment_tables(h);
+    hipError_t e = hipMalloc(&ctx->d_seg_tables, sizeof(framesum::SegTables));
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_seg_tables, h, sizeof(framesum::SegTables), hipMemcpyHostToDevice);
+    delete h;
+    if (e != hipSuccess) {
+        (void)hipFree(ctx->d_seg_tables);
+        ctx->d_seg_tables = nullptr;
+        return hip_err(ctx, e, "frame build: table upload");
+    }
+    return FS_SUCCESS;
+}
+
 // Stage a checked batch and enqueue its copy and its one kernel on `stream`.
 static fs_status segment_enqueue(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_sends,
                                  const framesum::segment::Layout& L, const uint8_t* payload, uint32_t mtu, uint32_t flags,
                                  uint32_t align, uint8_t* frames, uint64_t* offsets, uint32_t* lengths, fs_digest* out,
                                  uint8_t* status, hipStream_t stream) {
     namespace seg = framesum::segment;
-    if (!ctx->d_seg_tables) {
-        framesum::SegTables* h = new (std::nothrow) framesum::SegTables;
-        if (!h) return set_err(ctx, FS_E_NOMEM, "fs_segment_batch: out of host memory");
-        framesum::build_segment_tables(h);
-        hipError_t e = hipMalloc(&ctx->d_seg_tables, sizeof(framesum::SegTables));
-        if (e == hipSuccess) e = hipMemcpy(ctx->d_seg_tables, h, sizeof(framesum::SegTables), hipMemcpyHostToDevice);
-        delete h;
-        if (e != hipSuccess) {
-            (void)hipFree(ctx->d_seg_tables);
-            ctx->d_seg_tables = nullptr;
-            return hip_err(ctx, e, "fs_segment_batch: table upload");
-        }
-    }
+    const fs_status tst = seg_tables(ctx);
+    if (tst != FS_SUCCESS) return tst;
     const seg::Block b = seg::block_of(n_sends, L.id_entries);
     SegStage* sg = nullptr;
     const fs_status st = stage_block(ctx, b.bytes, &sg);

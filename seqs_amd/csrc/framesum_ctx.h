@@ -152,6 +152,9 @@ void drain_host_streams(fs_ctx* ctx);
 // caller fills `h`, copies it to `d`, sets `used` and records `done` behind its last reader.
 // framesum_api_tx.cpp.
 fs_status stage_block(fs_ctx* ctx, uint64_t bytes, SegStage** out);
+// fs_ctx::d_seg_tables, built and uploaded on the first call of a frame-building kernel
+// (fs_segment_batch, fs_send_rings_batch). framesum_api_tx.cpp.
+fs_status seg_tables(fs_ctx* ctx);
 
 // One launch of the context's kernel choice.
 // `force` < 0: the context's kernel choice (fs_ctx_set_kernel).

@@ -86,6 +86,15 @@ hipError_t launch_segment(const uint8_t* d_block, const segment::Block& b, uint3
                           uint8_t* status, uint32_t mtu, uint32_t flags, uint32_t align, const SegTables* tables,
                           int workgroups, hipStream_t stream);
 
+// ---- Ring send (framesum_send.hip). One launch that builds the n_frames frames of a staged batch of
+// sockets from their TX rings in `rings`: `d_block` is the device copy of the block send::stage()
+// filled (framesum_send.h: n_recs records, one per socket that makes a frame), `b` its layout. The
+// tables are the TX frame build's. `workgroups` caps the grid.
+hipError_t launch_send_rings(const uint8_t* d_block, const segment::Block& b, uint32_t n_recs, uint32_t n_frames,
+                             const uint8_t* rings, uint8_t* frames, uint64_t* offsets, uint32_t* lengths, void* out,
+                             uint8_t* status, uint32_t mtu, uint32_t flags, uint32_t align, const SegTables* tables,
+                             int workgroups, hipStream_t stream);
+
 // ---- RX coalesce (framesum_coalesce.hip). The launches that follow a batch's digest launch on
 // `stream`: classify, the scan's three steps and the copy (fs_coalesce_batch in include/framesum.h).
 // `status`: the batch's verdicts, as that digest launch writes them. `scratch`: coalesce_scratch(n).bytes

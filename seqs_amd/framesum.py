@@ -23,8 +23,9 @@ import numpy as np
 from .abi import (  # noqa: F401 (re-exported: this module is the binding's public face)
     DELIVER_MAX_SOCKS, DELIVER_PROTOTYPES, DIGEST_DTYPE, EXPORTED_SYMBOLS, FCS_APPEND, FILL_CSUM, FLOW_DTYPE,
     FLOW_TOTALS_DTYPE, FS_E_HIP, FS_E_INVALID, FS_E_NODEVICE, FS_E_NOMEM, FS_ERR_FCS, FS_SUCCESS, NO_FLOW, NO_RUN,
-    PROTOTYPES, RUN_DTYPE, RX_FCS, SEGMENT_MAX_FRAMES, SEND_DTYPE, SOCK_DTYPE, SOCK_OUT_DTYPE, TEST_LIB_PATH,
-    TOTALS_DTYPE, VERDICTS, FramesumError, lib_path, load_library, sock_key,
+    PROTOTYPES, RUN_DTYPE, RX_FCS, SEGMENT_MAX_FRAMES, SEND_DTYPE, SEND_MAX_SOCKS, SEND_NONE, SEND_RINGS_PROTOTYPES,
+    SOCK_DTYPE, SOCK_OUT_DTYPE, TEST_LIB_PATH, TOTALS_DTYPE, TX_ACK, TX_FIN, TX_PSH, TX_SOCK_DTYPE, TX_SOCK_OUT_DTYPE,
+    VERDICTS, FramesumError, lib_path, load_library, sock_key,
 )
 
 _vp, _u64 = ctypes.c_void_p, ctypes.c_uint64
@@ -503,6 +504,66 @@ class Engine(_Handle):
                 _array_ptr(marks) if delivered else None)
         return (socks_out, marks, *self._rx_host(_RX_DELIVER, frames, offsets, lengths, mtu, flags, payload, args))
 
+    # ---- TCP segments from socket TX rings (include/framesum_send.h) ------------
+    @staticmethod
+    def send_rings_layout(socks: np.ndarray, flags: int = 0, align: int = 1):
+        """(n_frames, frames_bytes, socks_out) of a batch of sockets (fs_send_rings_layout): host-only
+        arithmetic, see the module's send_rings_layout."""
+        return send_rings_layout(socks, flags, align)
+
+    def _send_rings(self, host: bool, socks, rings, mtu, flags, align, frames, stream):
+        """The one path of send_rings_device and send_rings_host: the layout, the frame buffer and
+        the four arrays (tensors on rings' device, or numpy arrays), and the call."""
+        socks = np.ascontiguousarray(socks, dtype=TX_SOCK_DTYPE)
+        n_frames, nbytes, _ = send_rings_layout(socks, flags, align)
+        socks_out = np.zeros(int(socks.size), dtype=TX_SOCK_OUT_DTYPE)
+        if host:
+            rings = np.ascontiguousarray(rings, dtype=np.uint8)
+            if frames is None:
+                frames = np.zeros(nbytes, dtype=np.uint8)
+            assert isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.flags["C_CONTIGUOUS"]
+            assert frames.flags["WRITEABLE"], "send_rings_host writes into `frames`"
+            arrays = [np.zeros(n_frames, dtype=d) for d in (np.uint64, np.uint32, DIGEST_DTYPE, np.uint8)]
+            ptr, size, tail = _array_ptr, (lambda a: a.nbytes), ()
+        else:
+            import torch
+
+            dev = rings.device
+            assert rings.is_cuda and rings.dtype == torch.uint8 and rings.is_contiguous()
+            if frames is None:
+                frames = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            assert frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous()
+            arrays = [torch.empty((n_frames,), dtype=torch.int64, device=dev),
+                      torch.empty((n_frames,), dtype=torch.int32, device=dev), *_result_tensors(n_frames, dev, None, None)]
+            if stream is None:
+                stream = torch.cuda.current_stream(dev)
+            ptr, size, tail = _tensor_ptr, (lambda t: int(t.numel())), (_stream_ptr(stream),)
+        name = "fs_send_rings_batch_host" if host else "fs_send_rings_batch"
+        st = getattr(self.lib, name)(self._ctx, _array_ptr(socks), int(socks.size), ptr(rings), size(rings), mtu, flags, align,
+                                     ptr(frames), size(frames), *map(ptr, arrays), _array_ptr(socks_out), *tail)
+        self._check(st, name)
+        return (frames, *arrays, socks_out)
+
+    def send_rings_device(self, socks: np.ndarray, rings, mtu: int = 0, flags: int = 0, align: int = 1, stream=None,
+                          frames=None):
+        """Build the TCP segments of `socks` (a TX_SOCK_DTYPE array on the host: header template,
+        mss, where in `rings` the socket's TX ring lies, its read position and buffered bytes, and
+        the connection state) straight from the uint8 CUDA tensor `rings` (fs_send_rings_batch): per
+        socket min(buffered, window room, max_frames * mss) bytes go out in mss-sized frames whose
+        payload is read across the ring's end, with Seq = snd_nxt + k mss, Ack = rcv_nxt, Window =
+        rcv_wnd, the TX_* flags, both checksums and (flags FCS_APPEND) the FCS. `frames`: a uint8
+        CUDA tensor to build into, else a new one. Returns (frames, offsets int64, lengths int32,
+        out (n, 2) int32, status uint8) device tensors and socks_out, a TX_SOCK_OUT_DTYPE numpy
+        array that is complete when the call returns; the rest is asynchronous on `stream`."""
+        return self._send_rings(False, socks, rings, mtu, flags, align, frames, stream)
+
+    def send_rings_host(self, socks: np.ndarray, rings: np.ndarray, mtu: int = 0, flags: int = 0, align: int = 1,
+                        frames: Optional[np.ndarray] = None):
+        """send_rings_device from and to host memory (fs_send_rings_batch_host). `frames`: a writable
+        uint8 array to build into, else a new zeroed one. Returns (frames, offsets uint64, lengths
+        uint32, digests, status, socks_out) numpy arrays."""
+        return self._send_rings(True, socks, rings, mtu, flags, align, frames, None)
+
     # ---- host-staged path (numpy in, numpy out) -----------------------------
     def host_empty(self, shape, dtype=np.uint8) -> np.ndarray:
         """A numpy array in pinned host memory (fs_host_alloc), freed with the array."""
@@ -620,6 +681,38 @@ def segment_layout(sends: np.ndarray, flags: int = 0, align: int = 4):
     if st != FS_SUCCESS:
         raise FramesumError(f"fs_segment_layout failed ({st}): {lib.fs_last_error(None).decode()}")
     return int(n.value), int(nbytes.value)
+
+
+def send_rings_layout(socks: np.ndarray, flags: int = 0, align: int = 1):
+    """(n_frames, frames_bytes, socks_out) a batch of sockets (TX_SOCK_DTYPE) needs and gives
+    (fs_send_rings_layout, host-only arithmetic: no device is touched): socks_out is the
+    TX_SOCK_OUT_DTYPE array the batch call writes. Raises FramesumError for an invalid socket, flags
+    or align."""
+    socks = np.ascontiguousarray(socks, dtype=TX_SOCK_DTYPE)
+    lib = load_library()
+    n, nbytes = _u64(), _u64()
+    socks_out = np.zeros(int(socks.size), dtype=TX_SOCK_OUT_DTYPE)
+    st = lib.fs_send_rings_layout(_array_ptr(socks), int(socks.size), flags, align, ctypes.byref(n), ctypes.byref(nbytes),
+                                  _array_ptr(socks_out))
+    if st != FS_SUCCESS:
+        raise FramesumError(f"fs_send_rings_layout failed ({st}): {lib.fs_last_error(None).decode()}")
+    return int(n.value), int(nbytes.value), socks_out
+
+
+def tx_sock_from(sock_out, tx=None, **fields) -> np.ndarray:
+    """TX_SOCK_DTYPE record(s) whose receive side is what a delivery left: rcv_nxt and rcv_wnd (=
+    ring_free, the room of the RX ring) come from `sock_out`, the SOCK_OUT_DTYPE record(s) of
+    deliver_flows_device / deliver_flows_host. `tx`: the record(s) to start from (the socket's
+    template, TX ring and send state), else zeros; `fields` set further fields, e.g. flags=TX_ACK
+    for the ACK that answers the delivery."""
+    sock_out = np.atleast_1d(np.asarray(sock_out, dtype=SOCK_OUT_DTYPE))
+    res = np.zeros(sock_out.size, dtype=TX_SOCK_DTYPE) if tx is None else \
+        np.atleast_1d(np.array(tx, dtype=TX_SOCK_DTYPE, copy=True))
+    assert res.size == sock_out.size, "one TX record per delivery record"
+    res["rcv_nxt"], res["rcv_wnd"] = sock_out["rcv_nxt"], sock_out["ring_free"]
+    for name, value in fields.items():
+        res[name] = value
+    return res
 
 
 def _records(t, dtype) -> np.ndarray:
