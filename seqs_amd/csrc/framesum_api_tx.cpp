@@ -1,5 +1,8 @@
 // framesum C ABI (include/framesum.h) -- the TX frame build: fs_segment_layout, fs_segment_batch and
-// fs_segment_batch_host (kernel: framesum_segment.hip; checks and layout: framesum_segment.h).
+// fs_segment_batch_host (kernel: framesum_segment.hip; checks and layout: framesum_segment.h), and
+// what they share with the ring send (framesum_api_send.cpp): the staging blocks, the tables, the
+// enqueue of a staged batch and the host form's device round trip.
+#include <functional>
 #include <new>
 #include <string>
 
@@ -75,29 +78,76 @@ fs_status framesum::host::seg_tables(fs_ctx* ctx) {
     return FS_SUCCESS;
 }
 
-// Stage a checked batch and enqueue its copy and its one kernel on `stream`.
-static fs_status segment_enqueue(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_sends,
-                                 const framesum::segment::Layout& L, const uint8_t* payload, uint32_t mtu, uint32_t flags,
-                                 uint32_t align, uint8_t* frames, uint64_t* offsets, uint32_t* lengths, fs_digest* out,
-                                 uint8_t* status, hipStream_t stream) {
-    namespace seg = framesum::segment;
+fs_status framesum::host::tx_enqueue(fs_ctx* ctx, uint64_t block_bytes, const std::function<void(uint8_t*)>& fill,
+                                     const std::function<hipError_t(const uint8_t*, int)>& launch, const char* launch_what,
+                                     hipStream_t stream) {
     const fs_status tst = seg_tables(ctx);
     if (tst != FS_SUCCESS) return tst;
-    const seg::Block b = seg::block_of(n_sends, L.id_entries);
     SegStage* sg = nullptr;
-    const fs_status st = stage_block(ctx, b.bytes, &sg);
+    const fs_status st = stage_block(ctx, block_bytes, &sg);
     if (st != FS_SUCCESS) return st;
-    seg::stage(sends, n_sends, flags, align, b, sg->h);
-    FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, b.bytes, hipMemcpyHostToDevice, stream));
+    fill(sg->h);
+    FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, block_bytes, hipMemcpyHostToDevice, stream));
     // two workgroups per CU (their tables fit its LDS twice) unless fs_ctx_set_workgroups caps the grid
     const int wgs = ctx->workgroups > 0 && ctx->workgroups < 2 * ctx->num_cus ? ctx->workgroups : 2 * ctx->num_cus;
     sg->used = true;  // (from here on the block may be read by queued work)
-    const hipError_t le = framesum::launch_segment(sg->d, b, n_sends, (uint32_t)L.n_frames, payload, frames, offsets, lengths,
-                                                   out, status, mtu, flags, align, ctx->d_seg_tables, wgs, stream);
+    const hipError_t le = launch(sg->d, wgs);
     const hipError_t re = hipEventRecord(sg->done, stream);
-    if (le != hipSuccess) return hip_err(ctx, le, "fs_segment_batch: launch");
+    if (le != hipSuccess) return hip_err(ctx, le, launch_what);
     if (re != hipSuccess) return hip_err(ctx, re, "hipEventRecord(sg->done, stream)");
     return FS_SUCCESS;
+}
+
+fs_status framesum::host::tx_host_call(fs_ctx* ctx, const uint8_t* src, uint64_t lo, uint64_t hi, uint64_t n,
+                                       uint64_t frames_bytes, bool gaps, uint8_t* frames, uint64_t* offsets, uint32_t* lengths,
+                                       fs_digest* out, uint8_t* status,
+                                       const std::function<fs_status(const TxDevice&)>& enqueue) {
+    fs_status st = begin_host_call(ctx);
+    if (st == FS_SUCCESS) st = ctx->seg_payload.grow(ctx, hi - lo);
+    if (st == FS_SUCCESS) st = ctx->seg_frames.grow(ctx, frames_bytes);
+    if (st == FS_SUCCESS) st = ctx->seg_arrays.grow(ctx, n * 21);
+    if (st != FS_SUCCESS) return st;
+    ctx->host_dirty = true;  // until this call has waited for all of its work
+    const hipStream_t ks = ctx->compute_stream;
+    // pinned memory (fs_host_alloc) is copied from and to directly; pageable memory goes through the
+    // runtime's own pinned staging
+    if (hi > lo) FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->seg_payload.p, src + lo, hi - lo, hipMemcpyHostToDevice, ks));
+    // the kernel writes frame and FCS bytes only: when the slots leave gaps (align > 1), the span
+    // goes in first so that the copy back returns the caller's own bytes there
+    if (gaps) FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->seg_frames.p, frames, frames_bytes, hipMemcpyHostToDevice, ks));
+    uint64_t* d_off = ctx->seg_arrays.as<uint64_t>();
+    fs_digest* d_out = ctx->seg_arrays.as<fs_digest>(n * 8);
+    uint32_t* d_len = ctx->seg_arrays.as<uint32_t>(n * 16);
+    uint8_t* d_st = ctx->seg_arrays.p + n * 20;
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(ctx->seg_payload.p) - lo);
+    st = enqueue(TxDevice{base, ctx->seg_frames.p, offsets ? d_off : nullptr, lengths ? d_len : nullptr,
+                          out ? d_out : nullptr, status ? d_st : nullptr, ks});
+    if (st != FS_SUCCESS) {
+        drain_host_streams(ctx);
+        return st;
+    }
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(frames, ctx->seg_frames.p, frames_bytes, hipMemcpyDeviceToHost, ks));
+    if (offsets) FS_HIP_DRAIN(ctx, hipMemcpyAsync(offsets, d_off, n * 8, hipMemcpyDeviceToHost, ks));
+    if (lengths) FS_HIP_DRAIN(ctx, hipMemcpyAsync(lengths, d_len, n * 4, hipMemcpyDeviceToHost, ks));
+    if (out) FS_HIP_DRAIN(ctx, hipMemcpyAsync(out, d_out, n * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
+    if (status) FS_HIP_DRAIN(ctx, hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ks));
+    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
+    ctx->host_dirty = false;
+    return FS_SUCCESS;
+}
+
+// Stage a checked batch and enqueue its copy and its one kernel.
+static fs_status segment_enqueue(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_sends,
+                                 const framesum::segment::Layout& L, uint32_t mtu, uint32_t flags, uint32_t align,
+                                 const TxDevice& t) {
+    namespace seg = framesum::segment;
+    const seg::Block b = seg::block_of(n_sends, L.id_entries);
+    const auto fill = [&](uint8_t* h_block) { seg::stage(sends, n_sends, flags, align, b, h_block); };
+    const auto launch = [&](const uint8_t* d_block, int workgroups) {
+        return framesum::launch_segment(d_block, b, n_sends, (uint32_t)L.n_frames, t.src, t.frames, t.offsets, t.lengths, t.out,
+                                        t.status, mtu, flags, align, ctx->d_seg_tables, workgroups, t.stream);
+    };
+    return tx_enqueue(ctx, b.bytes, std::ref(fill), std::ref(launch), "fs_segment_batch: launch", t.stream);
 }
 
 fs_status fs_segment_layout(const fs_tx_send* sends, uint32_t n_sends, uint32_t flags, uint32_t align, uint64_t* n_frames,
@@ -143,8 +193,8 @@ fs_status fs_segment_batch(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_send
                                       frames_bytes, L);
     if (st != FS_SUCCESS) return st;
     FS_HIP(ctx, hipSetDevice(ctx->device));
-    return segment_enqueue(ctx, sends, n_sends, L, payload, mtu, flags, align, frames, offsets, lengths, out, status,
-                           reinterpret_cast<hipStream_t>(stream));
+    return segment_enqueue(ctx, sends, n_sends, L, mtu, flags, align,
+                           TxDevice{payload, frames, offsets, lengths, out, status, reinterpret_cast<hipStream_t>(stream)});
 }
 
 fs_status fs_segment_batch_host(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n_sends, const uint8_t* payload,
@@ -167,38 +217,7 @@ fs_status fs_segment_batch_host(fs_ctx* ctx, const fs_tx_send* sends, uint32_t n
         hi = e > hi ? e : hi;
     }
     if (hi <= lo) lo = hi = 0;
-    const uint64_t n = L.n_frames;
-    fs_status st = begin_host_call(ctx);
-    if (st == FS_SUCCESS) st = ctx->seg_payload.grow(ctx, hi - lo);
-    if (st == FS_SUCCESS) st = ctx->seg_frames.grow(ctx, L.frames_bytes);
-    if (st == FS_SUCCESS) st = ctx->seg_arrays.grow(ctx, n * 21);
-    if (st != FS_SUCCESS) return st;
-    ctx->host_dirty = true;  // until this call has waited for all of its work
-    const hipStream_t ks = ctx->compute_stream;
-    // pinned memory (fs_host_alloc) is copied from and to directly; pageable memory goes through the
-    // runtime's own pinned staging
-    if (hi > lo) FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->seg_payload.p, payload + lo, hi - lo, hipMemcpyHostToDevice, ks));
-    // the kernel writes frame and FCS bytes only: when the slots leave gaps (align > 1), the span
-    // goes in first so that the copy back returns the caller's own bytes there
-    if (L.written != L.frames_bytes)
-        FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->seg_frames.p, frames, L.frames_bytes, hipMemcpyHostToDevice, ks));
-    uint64_t* d_off = ctx->seg_arrays.as<uint64_t>();
-    fs_digest* d_out = ctx->seg_arrays.as<fs_digest>(n * 8);
-    uint32_t* d_len = ctx->seg_arrays.as<uint32_t>(n * 16);
-    uint8_t* d_st = ctx->seg_arrays.p + n * 20;
-    const uint8_t* base = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(ctx->seg_payload.p) - lo);
-    st = segment_enqueue(ctx, sends, n_sends, L, base, mtu, flags, align, ctx->seg_frames.p, offsets ? d_off : nullptr,
-                         lengths ? d_len : nullptr, out ? d_out : nullptr, status ? d_st : nullptr, ks);
-    if (st != FS_SUCCESS) {
-        drain_host_streams(ctx);
-        return st;
-    }
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(frames, ctx->seg_frames.p, L.frames_bytes, hipMemcpyDeviceToHost, ks));
-    if (offsets) FS_HIP_DRAIN(ctx, hipMemcpyAsync(offsets, d_off, n * 8, hipMemcpyDeviceToHost, ks));
-    if (lengths) FS_HIP_DRAIN(ctx, hipMemcpyAsync(lengths, d_len, n * 4, hipMemcpyDeviceToHost, ks));
-    if (out) FS_HIP_DRAIN(ctx, hipMemcpyAsync(out, d_out, n * sizeof(fs_digest), hipMemcpyDeviceToHost, ks));
-    if (status) FS_HIP_DRAIN(ctx, hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ks));
-    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
-    ctx->host_dirty = false;
-    return FS_SUCCESS;
+    const auto enqueue = [&](const TxDevice& t) { return segment_enqueue(ctx, sends, n_sends, L, mtu, flags, align, t); };
+    return tx_host_call(ctx, payload, lo, hi, L.n_frames, L.frames_bytes, L.written != L.frames_bytes, frames, offsets,
+                        lengths, out, status, std::ref(enqueue));
 }

@@ -3,7 +3,7 @@
 // alignment, a frame's header load and classification, the payload copy by 16 lanes, and the four
 // gather steps -- classify, the scan of the partials, apply, copy -- written once over a mode that
 // each file supplies, with the launch arguments and the scratch layout the two families have in
-// common. (framesum_segment.hip takes Piece, load_at and store_at from here.) HIP only; the
+// common. (framesum_tx_dev.h takes Piece, load_at and store_at from here.) HIP only; the
 // arithmetic these call is in framesum_coalesce.h, which compiles without HIP.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <string>
 
 #include "../../include/framesum.h"
@@ -155,6 +156,35 @@ fs_status stage_block(fs_ctx* ctx, uint64_t bytes, SegStage** out);
 // fs_ctx::d_seg_tables, built and uploaded on the first call of a frame-building kernel
 // (fs_segment_batch, fs_send_rings_batch). framesum_api_tx.cpp.
 fs_status seg_tables(fs_ctx* ctx);
+
+// Where a frame-building call (fs_segment_batch, fs_send_rings_batch and their host forms) reads and
+// writes on the device: `src` is what the records' byte offsets count in (the payload, the rings), the
+// four result arrays are nullable.
+struct TxDevice {
+    const uint8_t* src;
+    uint8_t* frames;
+    uint64_t* offsets;
+    uint32_t* lengths;
+    fs_digest* out;
+    uint8_t* status;
+    hipStream_t stream;
+};
+// What such a call enqueues on `stream` for a checked batch: the tables, a staging block of `block_bytes`
+// bytes that `fill` fills, its copy to the device, the one kernel that `launch` starts on the device
+// copy with at most `workgroups` workgroups, and the block's event behind it. `launch_what` names a
+// failed launch in the error text. (Pass the callables by std::ref: nothing is allocated then.)
+// framesum_api_tx.cpp.
+fs_status tx_enqueue(fs_ctx* ctx, uint64_t block_bytes, const std::function<void(uint8_t* h_block)>& fill,
+                     const std::function<hipError_t(const uint8_t* d_block, int workgroups)>& launch,
+                     const char* launch_what, hipStream_t stream);
+// The device round trip of such a call's host form, on the compute stream: bytes [lo, hi) of `src`
+// go to the device, and the caller's frames span when the slots leave `gaps` (the kernel writes frame
+// and FCS bytes only); `enqueue` gets the device buffers, with `src` rebased so that the records'
+// offsets hold; the frames and the result arrays the caller passed (n_frames entries) come back, and
+// everything queued is waited for. framesum_api_tx.cpp.
+fs_status tx_host_call(fs_ctx* ctx, const uint8_t* src, uint64_t lo, uint64_t hi, uint64_t n_frames, uint64_t frames_bytes,
+                       bool gaps, uint8_t* frames, uint64_t* offsets, uint32_t* lengths, fs_digest* out, uint8_t* status,
+                       const std::function<fs_status(const TxDevice&)>& enqueue);
 
 // One launch of the context's kernel choice.
 // `force` < 0: the context's kernel choice (fs_ctx_set_kernel).

@@ -67,7 +67,8 @@ hipError_t launch_digest(const uint8_t* frames, const uint64_t* offsets, const u
 hipError_t launch_deinterleave(const uint8_t* gathered, uint32_t nshards, uint64_t n, void* out, uint8_t* status,
                                hipStream_t stream, uint64_t i0 = 0, uint64_t i1 = ~0ull);
 
-// ---- TX frame build (framesum_segment.hip). The kernel's CRC zero-shift tables Z_1, Z_2, Z_4, ...
+// ---- TX frame build (framesum_segment.hip; the device code it shares with the ring send:
+// framesum_tx_dev.h). The kernels' CRC zero-shift tables Z_1, Z_2, Z_4, ...
 // Z_32768 (tables 0..15) and Z_12 (table 16) as their one-bit basis, basis[t][b][j] = Z_k[b][1 << j]:
 // every workgroup expands them into LDS.
 constexpr uint32_t kSegTableCount = 17, kSegTableZ12 = 16;

@@ -2,8 +2,9 @@
 // so that it compiles on its own, like framesum_plan.h and framesum_choice.h: the validation of a
 // send, the frames a send makes, the prefix of frame indices and byte bases per send, the map from
 // a frame index back to (send, k), and the block of per-send records a call stages for the kernel
-// (framesum_segment.hip reads exactly these structs). tests/csrc/test_segment.cpp builds it alone
-// under ASan + UBSan.
+// (the kernel reads exactly these structs). The ring send's arithmetic (framesum_send.h) takes the
+// chunk of a byte count, the block's layout and the staged ID powers from here.
+// tests/csrc/test_segment.cpp builds it alone under ASan + UBSan.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -64,11 +65,13 @@ inline uint32_t frames_of(const fs_tx_send& s) {
     if (s.mss == 0 || s.payload_len == 0) return 1;
     return (uint32_t)(((uint64_t)s.payload_len + s.mss - 1) / s.mss);
 }
-inline uint32_t chunk_of(const fs_tx_send& s, uint32_t k) {
-    if (s.mss == 0) return s.payload_len;
-    const uint64_t lo = (uint64_t)k * s.mss;
-    return lo >= s.payload_len ? 0u : (uint32_t)(s.payload_len - lo < s.mss ? s.payload_len - lo : s.mss);
+// bytes [k mss, (k + 1) mss) of `total` (none behind its end); mss == 0: all of them
+inline uint32_t chunk_at(uint32_t total, uint32_t mss, uint32_t k) {
+    if (mss == 0) return total;
+    const uint64_t lo = (uint64_t)k * mss;
+    return lo >= total ? 0u : (uint32_t)(total - lo < mss ? total - lo : mss);
 }
+inline uint32_t chunk_of(const fs_tx_send& s, uint32_t k) { return chunk_at(s.payload_len, s.mss, k); }
 
 enum Bad : int {
     kGood = 0,
@@ -178,13 +181,24 @@ static_assert(sizeof(fs_tx_send) == 72 && offsetof(fs_tx_send, mss) == 54 && off
 struct Block {
     uint64_t recs_at = 0, prefix_at = 0, ids_at = 0, bytes = 0;
 };
-inline Block block_of(uint32_t n_sends, uint64_t id_entries) {
+// n_recs records of rec_bytes each: the layout of this call's block and of the ring send's
+inline Block block_of(uint32_t n_recs, uint64_t rec_bytes, uint64_t id_entries) {
     Block b;
     b.recs_at = 0;
-    b.prefix_at = (uint64_t)n_sends * sizeof(SendRec);
-    b.ids_at = b.prefix_at + ((uint64_t)n_sends + 1) * 4;
+    b.prefix_at = (uint64_t)n_recs * rec_bytes;
+    b.ids_at = b.prefix_at + ((uint64_t)n_recs + 1) * 4;
     b.bytes = (b.ids_at + id_entries * 2 + 63) & ~63ull;
     return b;
+}
+inline Block block_of(uint32_t n_sends, uint64_t id_entries) { return block_of(n_sends, sizeof(SendRec), id_entries); }
+// A record's staged ID powers, ceil(frames / kIdStride) of them from ids[id_at] on: the IDs of its
+// frames 0, kIdStride, 2 kIdStride, ... Returns the index behind them.
+inline uint64_t stage_ids(uint16_t id, uint32_t frames, uint16_t* ids, uint64_t id_at) {
+    for (uint32_t k = 0; k < frames; k += kIdStride) {
+        ids[id_at++] = id;
+        id = prand16_stride(id);
+    }
+    return id_at;
 }
 // Fill a block of block_of(...).bytes bytes at `dst` from a batch layout() found valid.
 inline void stage(const fs_tx_send* sends, uint32_t n_sends, uint32_t flags, uint32_t align, const Block& b, uint8_t* dst) {
@@ -205,11 +219,7 @@ inline void stage(const fs_tx_send* sends, uint32_t n_sends, uint32_t flags, uin
         r.id_at = (uint32_t)id_at;
         memcpy(&recs[i], &r, sizeof r);
         prefix[i] = (uint32_t)frame;
-        uint16_t id = (uint16_t)((s.hdr[18] << 8) | s.hdr[19]);
-        for (uint32_t k = 0; k < r.frames; k += kIdStride) {
-            ids[id_at++] = id;
-            id = prand16_stride(id);
-        }
+        id_at = stage_ids((uint16_t)((s.hdr[18] << 8) | s.hdr[19]), r.frames, ids, id_at);
         frame += r.frames;
         base += send_bytes(s, flags, align);
     }
@@ -217,11 +227,7 @@ inline void stage(const fs_tx_send* sends, uint32_t n_sends, uint32_t flags, uin
 }
 
 // Frame k of a staged send: its payload bytes, byte offset in `frames` and IPv4 ID.
-inline uint32_t rec_chunk(const SendRec& r, uint32_t k) {
-    if (r.mss == 0) return r.payload_len;
-    const uint64_t lo = (uint64_t)k * r.mss;
-    return lo >= r.payload_len ? 0u : (uint32_t)(r.payload_len - lo < r.mss ? r.payload_len - lo : r.mss);
-}
+inline uint32_t rec_chunk(const SendRec& r, uint32_t k) { return chunk_at(r.payload_len, r.mss, k); }
 inline uint64_t rec_frame_offset(const SendRec& r, uint32_t k, uint32_t flags, uint32_t align) {
     const uint32_t h = r.hdr[23] == 17 ? kUdpHdr : kTcpHdr;
     return r.frame_base + (uint64_t)k * slot_bytes(h + r.mss, flags, align);  // frames before k are full ones

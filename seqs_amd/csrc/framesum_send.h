@@ -2,8 +2,9 @@
 // that it compiles on its own, like framesum_segment.h and framesum_deliver.h: the checks of a socket,
 // the per-socket rule (how much goes out, in how many frames, with which flags, and the state after),
 // the layout, and the block of per-socket records a call stages for the kernel (framesum_send.hip
-// reads exactly these structs). The slots, the ID powers and the frame -> record search are the TX
-// frame build's (framesum_segment.h). tests/csrc/test_send.cpp builds it alone under ASan + UBSan.
+// reads exactly these structs). The slots, the chunks, the block's layout, the ID powers and the
+// frame -> record search are the TX frame build's (framesum_segment.h). tests/csrc/test_send.cpp builds
+// it alone under ASan + UBSan.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -100,10 +101,7 @@ inline Plan plan_of(const fs_tx_sock& s) {
     p.tcp_flags = (uint8_t)(kTcpAck | ((s.flags & FS_TX_PSH) && p.data ? kTcpPsh : 0) | (p.fin ? kTcpFin : 0));
     return p;
 }
-inline uint32_t chunk_of(const fs_tx_sock& s, const Plan& p, uint32_t k) {
-    const uint64_t lo = (uint64_t)k * s.mss;
-    return lo >= p.data ? 0u : (uint32_t)(p.data - lo < s.mss ? p.data - lo : s.mss);
-}
+inline uint32_t chunk_of(const fs_tx_sock& s, const Plan& p, uint32_t k) { return segment::chunk_at(p.data, s.mss, k); }
 // prand16 applied n times (n <= FS_SEGMENT_MAX_FRAMES): kIdStride steps at once, then the rest
 inline uint16_t advance_id(uint16_t id, uint32_t n) {
     for (; n >= segment::kIdStride; n -= segment::kIdStride) id = segment::prand16_stride(id);
@@ -196,15 +194,21 @@ struct RingRec {
 static_assert(sizeof(RingRec) == 96 && offsetof(RingRec, ring_off) == 56 && offsetof(RingRec, frame_base) == 72 &&
                   offsetof(RingRec, ring_size) == 84,
               "RingRec layout (the kernel reads it)");
+// What the frame body both kernels share (framesum_tx_dev.h) reads of a record lies where
+// segment::SendRec has it: the header, mss, the byte offset, the byte count, frames, frame_base, id_at.
+static_assert(offsetof(RingRec, hdr) == offsetof(segment::SendRec, hdr) &&
+                  offsetof(RingRec, mss) == offsetof(segment::SendRec, mss) &&
+                  offsetof(RingRec, ring_off) == offsetof(segment::SendRec, payload_off) &&
+                  offsetof(RingRec, data) == offsetof(segment::SendRec, payload_len) &&
+                  offsetof(RingRec, frames) == offsetof(segment::SendRec, frames) &&
+                  offsetof(RingRec, frame_base) == offsetof(segment::SendRec, frame_base) &&
+                  offsetof(RingRec, id_at) == offsetof(segment::SendRec, id_at),
+              "RingRec and SendRec agree in what the shared frame body reads");
 
 inline segment::Block block_of(uint32_t n_recs, uint64_t id_entries) {
-    segment::Block b;
-    b.recs_at = 0;
-    b.prefix_at = (uint64_t)n_recs * sizeof(RingRec);
-    b.ids_at = b.prefix_at + ((uint64_t)n_recs + 1) * 4;
-    b.bytes = (b.ids_at + id_entries * 2 + 63) & ~63ull;
-    return b;
+    return segment::block_of(n_recs, sizeof(RingRec), id_entries);
 }
+
 inline void put32(uint8_t* p, uint32_t v) {
     p[0] = (uint8_t)(v >> 24);
     p[1] = (uint8_t)(v >> 16);
@@ -247,11 +251,7 @@ inline void stage(const fs_tx_sock* socks, uint32_t n_socks, uint32_t flags, uin
         r.ring_rpos = s.ring_rpos;
         memcpy(&recs[n], &r, sizeof r);
         prefix[n++] = (uint32_t)frame;
-        uint16_t id = template_id(s);
-        for (uint32_t k = 0; k < p.frames; k += segment::kIdStride) {
-            ids[id_at++] = id;
-            id = segment::prand16_stride(id);
-        }
+        id_at = segment::stage_ids(template_id(s), p.frames, ids, id_at);
         frame += p.frames;
         base += sock_bytes(s, p, flags, align);
     }
@@ -260,10 +260,7 @@ inline void stage(const fs_tx_sock* socks, uint32_t n_socks, uint32_t flags, uin
 
 // Where frame k of a staged record reads: its chunk, the ring position of the chunk's first byte and
 // the chunk bytes that lie before the ring's end (>= chunk: the chunk does not wrap).
-inline uint32_t rec_chunk(const RingRec& r, uint32_t k) {
-    const uint64_t lo = (uint64_t)k * r.mss;
-    return lo >= r.data ? 0u : (uint32_t)(r.data - lo < r.mss ? r.data - lo : r.mss);
-}
+inline uint32_t rec_chunk(const RingRec& r, uint32_t k) { return segment::chunk_at(r.data, r.mss, k); }
 inline uint32_t rec_pos(const RingRec& r, uint32_t k) {
     return (uint32_t)(((uint64_t)r.ring_rpos + (uint64_t)k * r.mss) % r.ring_size);
 }

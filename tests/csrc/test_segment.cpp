@@ -171,6 +171,32 @@ int main() {
     }
     CHECK(seg::tile_frames(65536, 4096) == 16 && seg::tile_frames(1, 16) == 1 && seg::tile_frames(1u << 31, 4096) == 16 &&
           seg::tile_frames(100, 64) == 2);
+    // the helpers the ring send shares. A block: the records, n + 1 prefix entries, the ID powers, up to 64
+    {
+        const seg::Block b = seg::block_of(3, sizeof(seg::SendRec), 5), e = seg::block_of(0, sizeof(seg::SendRec), 0);
+        CHECK(b.recs_at == 0 && b.prefix_at == 3 * 88 && b.ids_at == 3 * 88 + 16 && b.bytes == 320);
+        CHECK(e.prefix_at == 0 && e.ids_at == 4 && e.bytes == 64);
+        CHECK(seg::block_of(3, 5).prefix_at == b.prefix_at && seg::block_of(3, 5).ids_at == b.ids_at && seg::block_of(3, 5).bytes == b.bytes);
+        CHECK(seg::block_of(3, 96, 5).prefix_at == 288 && seg::block_of(3, 96, 5).bytes == 320);
+        CHECK(seg::block_of(1, 88, 14).bytes == 128 && seg::block_of(1, 88, 15).bytes == 128 && seg::block_of(1, 88, 17).bytes == 192);
+        // a chunk: whole, the rest, nothing at k mss == total and behind; mss == 0: everything, for any k
+        CHECK(seg::chunk_at(1000, 100, 0) == 100 && seg::chunk_at(1000, 100, 9) == 100 && seg::chunk_at(1000, 100, 10) == 0);
+        CHECK(seg::chunk_at(1001, 100, 10) == 1 && seg::chunk_at(1001, 100, 11) == 0 && seg::chunk_at(0, 100, 0) == 0);
+        CHECK(seg::chunk_at(1000, 0, 0) == 1000 && seg::chunk_at(1000, 0, 7) == 1000 && seg::chunk_at(0, 0, 0) == 0);
+        CHECK(seg::chunk_at(0xFFFFFFFFu, 65535, 65536) == 65535 && seg::chunk_at(0xFFFFFFFFu, 65535, 65537) == 0);
+        // the staged ID powers: ceil(frames / 64) entries from id_at on, and rec_id walks from them
+        for (uint32_t frames : {1u, 63u, 64u, 65u, 128u, 129u, 4096u}) {
+            std::vector<uint16_t> ids(2 + (frames + 63) / 64 + 1, 0xEEEE);
+            const uint64_t end = seg::stage_ids(0xBEEF, frames, ids.data(), 2);
+            CHECK(end == 2 + (frames + 63) / 64 && ids[0] == 0xEEEE && ids[1] == 0xEEEE && ids[end] == 0xEEEE);
+            seg::SendRec r{};
+            r.id_at = 2;
+            uint16_t id = 0xBEEF;
+            for (uint32_t k = 0; k < frames; ++k, id = seg::prand16(id)) CHECK(seg::rec_id(r, ids.data(), k) == id);
+        }
+        uint16_t none = 0xEEEE;
+        CHECK(seg::stage_ids(1, 0, &none, 0) == 0 && none == 0xEEEE);
+    }
     std::puts("segment checks OK");
     return 0;
 }

@@ -267,10 +267,36 @@ static void test_batches() {
     CHECK(outs[1].first_frame == FS_SEND_NONE && outs[1].snd_nxt == 1500 && outs[1].ring_rpos == 3 && outs[1].ip_id == 0x1234);
 }
 
+// The TX frame build's helpers as the ring send uses them: the block over 96-byte records, a record's
+// chunks, and its staged ID powers against segment::rec_id over a SendRec with the same id_at.
+static void test_shared_helpers() {
+    const seg::Block b = seg::block_of(3, sizeof(sd::RingRec), 5), s = seg::block_of(3, sizeof(seg::SendRec), 5);
+    CHECK(sizeof(sd::RingRec) == 96 && b.recs_at == 0 && b.prefix_at == 288 && b.ids_at == 304 && b.bytes == 320);
+    CHECK(s.prefix_at == 264 && s.ids_at == 280 && s.bytes == 320);
+    CHECK(sd::block_of(3, 5).prefix_at == b.prefix_at && sd::block_of(3, 5).bytes == b.bytes && seg::block_of(3, 5).ids_at == 280);
+    CHECK(seg::block_of(0, 96, 0).bytes == 64 && seg::block_of(2, 96, 26).bytes == 256 && seg::block_of(2, 96, 27).bytes == 320);
+    sd::RingRec r{};
+    r.mss = 100, r.data = 1000, r.id_at = 1;
+    CHECK(sd::rec_chunk(r, 9) == 100 && sd::rec_chunk(r, 10) == 0 && seg::chunk_at(1000, 100, 10) == 0);  // k mss == total
+    r.data = 1001;
+    CHECK(sd::rec_chunk(r, 10) == 1 && sd::rec_chunk(r, 11) == 0);
+    CHECK(seg::chunk_at(1001, 0, 0) == 1001 && seg::chunk_at(1001, 0, 3) == 1001);  // (mss == 0: no socket has it)
+    const fs_tx_sock k = sock(100, 0, 4096, 5, 1000);
+    CHECK(sd::chunk_of(k, sd::plan_of(k), 9) == 100 && sd::chunk_of(k, sd::plan_of(k), 10) == 0);
+    seg::SendRec as_send{};
+    as_send.id_at = r.id_at;
+    for (uint32_t frames : {1u, 64u, 65u, 200u, 4096u}) {
+        std::vector<uint16_t> ids(1 + (frames + 63) / 64, 0xEEEE);
+        CHECK(seg::stage_ids(0x1234, frames, ids.data(), 1) == ids.size() && ids[0] == 0xEEEE);
+        for (uint32_t f = 0; f < frames; ++f) CHECK(seg::rec_id(as_send, ids.data(), f) == sd::advance_id(0x1234, f));
+    }
+}
+
 int main() {
     test_rejections();
     test_rule();
     test_batches();
+    test_shared_helpers();
     if (g_failed) {
         std::printf("%d checks failed\n", g_failed);
         return 1;

@@ -144,6 +144,14 @@ def rejected_frames(seed=28):
     return socks, rng.integers(0, 256, 8292, dtype=np.uint8)
 
 
+def both_entry_point_cases():
+    """The batches built through fs_send_rings_batch and, linearised, through fs_segment_batch: every
+    head-piece length 1 to 49, the 1,024-byte lane stride and the two-piece loop, each unwrapped and
+    wrapped; and ten frames of 100 bytes that end 20 bytes before the ring's end, wrap inside a whole
+    piece of the last frame, and wrap inside the first frame's 4-byte head piece."""
+    return [chunk_lengths(), *(wrap_sweep(r) for r in (3076, 3111, 4095))]
+
+
 def oracle_cases():
     """Every case whose frames all pass RecvEth (case 7's are judged in the GPU test)."""
     yield from (wrap_sweep(r) for r in (3076, 3096, 3111, 3996, 4095))

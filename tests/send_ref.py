@@ -81,6 +81,20 @@ def frames_of(socks, rings: np.ndarray):
     return frames, outs
 
 
+def segment_sends(socks, rings: np.ndarray):
+    """The same frames asked of the TX frame build: (specs, payload) as segment_ref.make_sends and
+    segment_ref.expected take them, one send per socket that makes a frame. Its header is the template
+    with Seq, Ack, the window and the last frame's flags written in, its payload the socket's sent bytes
+    unwrapped (the sends' ranges lie back to back in `payload`), its mss the socket's."""
+    specs, blob = [], b""
+    for s in socks:
+        r = rule(s)
+        if r["S"]:
+            specs.append((template(s, r), len(blob), r["data"], s["mss"]))
+            blob += ring_bytes(rings, s, r["data"])
+    return specs, np.frombuffer(blob + b"\0", dtype=np.uint8)[:-1].copy()
+
+
 def expected(socks, rings: np.ndarray, mtu: int, flags: int, align: int, noise: np.ndarray):
     """(buffer, offsets, lengths, digests, status, socks_out) a build of `socks` (sock() dicts) into a
     copy of `noise` must give."""

@@ -96,6 +96,34 @@ def test_chunk_lengths(eng, align, flags):
     check_device(eng, socks, rings, 0, flags, align, lead=align == 1 and 5 or 64)
 
 
+# 2b ---- the same bytes through both entry points: one frame body, so the same frames
+@pytest.mark.parametrize("align,flags", [(1, FCS), (64, 0)])
+def test_segment_batch_builds_the_same_frames(eng, align, flags):
+    import torch
+
+    import segment_ref as sref
+    from seqs_amd import segment_layout, send_rings_layout
+
+    dev = torch.device("cuda:0")
+    for seed, (socks, rings) in enumerate(cases.both_entry_point_cases()):
+        recs = ref.socks_of(socks)
+        specs, payload = ref.segment_sends(socks, rings)  # (tests/test_send_host.py: these make the reference's frames)
+        sends = sref.make_sends(specs)
+        n, nbytes, _ = send_rings_layout(recs, flags, align)
+        assert (n, nbytes) == segment_layout(sends, flags, align) and n >= 10
+        noise = np.random.default_rng(seed).integers(0, 256, nbytes + TAIL, dtype=np.uint8)
+        ring_buf, seg_buf = torch.from_numpy(noise).to(dev), torch.from_numpy(noise).to(dev)
+        a = eng.send_rings_device(recs, torch.from_numpy(rings).to(dev), 0, flags, align, frames=ring_buf)
+        b = eng.segment_device(sends, torch.from_numpy(payload).to(dev), 0, flags, align, frames=seg_buf)
+        torch.cuda.synchronize()
+        got, want = ring_buf.cpu().numpy(), seg_buf.cpu().numpy()
+        bad = np.flatnonzero(got != want)
+        assert bad.size == 0, f"{bad.size} bytes differ, first at {bad[:8]}"
+        assert (got != noise).sum() > nbytes // 4  # (frames were built)
+        for name, x, y in zip(("offsets", "lengths", "digests", "status"), a[1:5], b[1:5]):
+            assert x.dtype == y.dtype and x.shape[0] == n and torch.equal(x, y), name
+
+
 # 3 ---- rings smaller than a piece
 def test_tiny_rings(eng):
     socks, rings = cases.tiny_rings()

@@ -128,6 +128,24 @@ def test_reference_frames_pass_the_oracle():
         assert f == len(frames)
 
 
+def test_derived_sends_make_the_references_frames():
+    # what tests/test_gpu_send_rings.py hands to fs_segment_batch for the same bytes
+    for socks, rings in cases.both_entry_point_cases():
+        specs, payload = ref.segment_sends(socks, rings)
+        frames, outs = ref.frames_of(socks, rings)
+        assert len(specs) == int((outs["n_frames"] > 0).sum()) > 0 and payload.size == int(outs["bytes"].sum())
+        pb = payload.tobytes()
+        mine = [f for hdr, off, ln, mss in specs for f in sref.send_frames(hdr, pb[off : off + ln], mss)]
+        assert mine == frames and len(frames) >= 10
+        for flags, align in ((ref.FCS_APPEND, 1), (0, 64)):
+            noise = np.random.default_rng(5).integers(0, 256, sref.layout([len(f) for f in frames], flags, align)[1] + 64,
+                                                      dtype=np.uint8)
+            a, b = sref.expected(specs, payload, 0, flags, align, noise), ref.expected(socks, rings, 0, flags, align, noise)
+            assert all(np.array_equal(x, y) for x, y in zip(a, b[:5]))
+        sends = sref.make_sends(specs)
+        assert np.array_equal(sends["mss"], [s["mss"] for s in socks if ref.rule(s)["S"]]) and (sends["hdr"][:, 23] == 6).all()
+
+
 def test_hand_computed_socket():
     # ring "0123456789abcdef" read from 'c': 10 bytes in frames of 4 -> "cdef" "0123" "45"
     rings = np.frombuffer(b"..0123456789abcdef", dtype=np.uint8)

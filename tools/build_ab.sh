@@ -9,7 +9,7 @@ name=$1; src=$2
 R=$(cd "$(dirname "$0")/.." && pwd)
 d=$(mktemp -d)/a/b/csrc; mkdir -p "$d" "$d/../../include"
 cp "$R"/seqs_amd/csrc/*.cpp "$R"/seqs_amd/csrc/*.h "$R"/seqs_amd/csrc/*.hip "$R"/seqs_amd/csrc/Makefile "$d"/
-cp "$R"/include/framesum.h "$d/../../include/"
+cp "$R"/include/*.h "$d/../../include/"
 if [ -f "$src" ]; then cp "$src" "$d/framesum_kernel.hip"; else git -C "$R" show "$src:seqs_amd/csrc/framesum_kernel.hip" > "$d/framesum_kernel.hip"; fi
 make -B -C "$d" lib OUT="$R/seqs_amd/lib/ab/libframesum_$name.so"
 ls -la "$R/seqs_amd/lib/ab/libframesum_$name.so"
