@@ -315,35 +315,7 @@ def test_sizes_around_the_wave_and_the_scan_block(eng, n):
 BIG = 65793  # 257 scan blocks and one frame
 
 
-def big_batch(flow_of, seed):
-    """One 64-byte TCP segment (10 bytes of payload) per entry of flow_of, back to back; a flow's
-    segments continue each other in batch order. Built with numpy, checksums by the C oracle."""
-    from oracle import coracle
-
-    rng = np.random.default_rng(seed)
-    n, n_flows = flow_of.size, int(flow_of.max()) + 1
-    hdr = rng.integers(0, 256, (n_flows, 54), dtype=np.uint8)
-    ids = np.arange(n_flows, dtype=np.uint32)
-    hdr[:, 12], hdr[:, 13], hdr[:, 14], hdr[:, 23], hdr[:, 46], hdr[:, 47] = 8, 0, 0x45, 6, 0x50, ACK
-    hdr[:, 16], hdr[:, 17] = 0, 50
-    for k in range(4):  # distinct keys: the flow's number is its source address
-        hdr[:, 26 + k] = (ids >> (24 - 8 * k)) & 0xFF
-    hdr[:, 34:38] = [0x10, 0x01, 0x00, 0x50]
-    frames = rng.integers(0, 256, (n, 64), dtype=np.uint8)
-    frames[:, :54] = hdr[flow_of]
-    by_flow = np.argsort(flow_of, kind="stable")
-    start = np.searchsorted(flow_of[by_flow], np.arange(n_flows))
-    rank = np.empty(n, dtype=np.int64)
-    rank[by_flow] = np.arange(n) - start[flow_of[by_flow]]
-    seq = (rng.integers(0, 1 << 32, n_flows, dtype=np.int64)[flow_of] + 10 * rank) % (1 << 32)
-    for k in range(4):
-        frames[:, 38 + k] = (seq >> (24 - 8 * k)) & 0xFF
-    frames[:, 18:20] = rng.integers(0, 256, (n, 2), dtype=np.uint8)
-    buf = np.concatenate([frames.reshape(-1), rng.integers(0, 256, 64, dtype=np.uint8)])
-    off = np.arange(n, dtype=np.uint64) * np.uint64(64)
-    ln = np.full(n, 64, dtype=np.uint32)
-    coracle.fill_batch(buf, off, ln, 0, coracle.FILL_CSUM)
-    return buf, off, ln
+from deliver_cases import big_batch  # noqa: E402  (the numpy builder, shared with the delivery's edge suite)
 
 
 BIG_SHAPES = {

@@ -33,6 +33,8 @@ import numpy as np
 import pytest
 
 import coalesce_ref as cref
+import deliver_cases as dcases
+import deliver_ref as dref
 import engines
 import flows_ref as fref
 import framegen
@@ -479,14 +481,34 @@ def rx_cases(fcs):
 
 @gpu
 @pytest.mark.parametrize("fcs", [False, True])
-@pytest.mark.parametrize("call", ["coalesce", "flows"])
+def sockets_of_the_flows(case, e):
+    """One socket per TCP flow of the batch (flows_ref.expected's dict `e`), expecting the Seq of the
+    flow's first frame; rings one sentinel byte apart in a small buffer of their own, every second one
+    too short for its flow. Returns (socks, rings_bytes)."""
+    socks, at = [], 1
+    for k, fl in enumerate(e["flows"]):
+        i = int(e["order"][int(fl["first_frame"])])
+        f = case.buf[int(case.off[i]) : int(case.off[i]) + int(case.ln[i])].tobytes()
+        if f[23] != 6:
+            continue
+        size = max(1, int(fl["payload_len"]) * (3 if k % 2 else 4) // 4)
+        socks.append(dcases.sock_of(f, dcases.seq_of(f), at, size, ring_wpos=size - 1 - k % size))
+        at += size + 1
+    return dref.socks_of(*socks), at + 2
+
+
+@gpu
+@pytest.mark.parametrize("fcs", [False, True])
+@pytest.mark.parametrize("call", ["coalesce", "flows", "deliver"])
 @pytest.mark.parametrize("which", PLACEMENTS)
 def test_rx_source_beyond_4gib(eng, big, which, call, fcs):
     """The frames read from beyond 2^32: payload with its noise margins, runs, (flows, order,) run_of,
-    totals, digests and verdicts against the restatement of the small copy."""
+    totals, digests and verdicts against the restatement of the small copy; for the delivery also
+    socks_out, delivered and the whole of a small rings buffer, one socket per TCP flow."""
     import torch
 
     import test_gpu_coalesce as tc
+    import test_gpu_deliver as td
     import test_gpu_flows as tf
 
     flags = cref.RX_FCS if fcs else 0
@@ -497,6 +519,12 @@ def test_rx_source_beyond_4gib(eng, big, which, call, fcs):
         e = ref.expected(case.buf, case.off, case.ln, 0, flags, noise, plead, room)
         assert e["n_runs"] >= 2 and e["payload_bytes"] > 0 and (k == 0 or (e["st"] != 0).any())
         ln_dev, noise_dev = dev(case.ln), dev(noise)
+        if call == "deliver":
+            socks, rings_bytes = sockets_of_the_flows(case, e)
+            rings = td.sentinel(rings_bytes, k)
+            e = dref.expected(case.buf, case.off, case.ln, 0, flags, noise, plead, room, socks, rings)
+            assert socks.size == e["n_flows"] >= 2 and (e["delivered"] == 1).any() and (k == 0 or (e["delivered"] == 2).any())
+            rings_dev = dev(rings)
         for label, bases in placements(case, big, which):
             assert_beyond(big, which, case.off, case.ln, bases)
             put_all(case, big, bases)
@@ -505,10 +533,86 @@ def test_rx_source_beyond_4gib(eng, big, which, call, fcs):
                 res = eng.coalesce_device(big, dev(case.off + bases), ln_dev, 0, flags, payload=pt[plead : plead + room])
                 torch.cuda.synchronize()
                 tc.compare(e, pt.cpu().numpy(), *res[1:])
+            elif call == "deliver":
+                rt = rings_dev.clone()
+                res = eng.deliver_flows_device(big, dev(case.off + bases), ln_dev, socks, rt, 0, flags,
+                                               payload=pt[plead : plead + room])
+                torch.cuda.synchronize()
+                td.compare_delivery(e, res[0], res[1], rt)
+                tf.compare(e, pt.cpu().numpy(), *res[3:])
             else:
                 res = eng.coalesce_flows_device(big, dev(case.off + bases), ln_dev, 0, flags, payload=pt[plead : plead + room])
                 torch.cuda.synchronize()
                 tf.compare(e, pt.cpu().numpy(), *res[1:])
+
+
+@gpu
+def test_deliver_rings_beyond_4gib(eng, big):
+    """The rings tensor longer than 4 GiB. Ring A has the maximal 2^31 bytes at ring_off 2^31 + 32 MiB,
+    so it spans offset 2^32: three 100-byte segments from wpos 2^31 - 100 wrap at its end; a second
+    call with wpos 2^31 - 32 MiB - 50 puts a payload across offset 2^32 itself. Ring B (4,096 bytes)
+    lies wholly beyond 2^32 and ends with the tensor. Every flow is in order and fits, so what is
+    expected is the closed form: byte j of a flow's payloads at (wpos + j) mod ring_size. Windows of
+    MARGIN bytes around every write are compared on the host; the rest of the tensor is checked on the
+    device to hold FILL still."""
+    import torch
+
+    import test_gpu_flows as tf
+    from seqs_amd import split_socks
+
+    rng = np.random.default_rng(4321)
+    A_OFF, A_SIZE, B_OFF, B_SIZE = (1 << 31) + (32 << 20), 1 << 31, BIG_BYTES - 4096, 4096
+    assert A_OFF < G < A_OFF + A_SIZE <= B_OFF and G < B_OFF and B_OFF + B_SIZE == big.numel()
+    hdrs = [fref.flow_header(rng, 0xA100), fref.flow_header(rng, 0xB100)]
+    seq = [(1 << 32) - 250, 5000]
+    wpos = {0: [A_SIZE - 100, 4000], 1: [A_SIZE - (32 << 20) - 50, None]}
+    big.fill_(FILL)
+    written = []
+    for call in (0, 1):
+        segs = [fref.segments(rng, hdrs[f], seq[f], [100] * 3) for f in (0, 1)]
+        frames = fref.finish([segs[g][k] for g, k in fref.interleave([range(3)] * 2)])
+        buf, off, ln = fref.pack(frames, lead=call + 1)
+        if wpos[1][1] is None:
+            wpos[1][1] = (4000 + 300) % B_SIZE
+        wa, wb = wpos[call]
+        assert A_OFF + wa < G < A_OFF + wa + 100 or call == 0
+        socks = dref.socks_of(dcases.sock_of(segs[0][0], seq[0], A_OFF, A_SIZE, ring_wpos=wa),
+                              dcases.sock_of(segs[1][0], seq[1], B_OFF, B_SIZE, ring_wpos=wb))
+        room = int(ln.sum())
+        noise = np.random.default_rng(call).integers(0, 256, room + 96, dtype=np.uint8)
+        e = fref.expected(buf, off, ln, 0, 0, noise, 0, room)
+        pt = dev(noise)
+        res = eng.deliver_flows_device(dev(buf), dev(off.astype(np.int64)), dev(ln.astype(np.int32)), socks, big,
+                                       payload=pt[:room])
+        torch.cuda.synchronize()
+        tf.compare(e, pt.cpu().numpy(), *res[3:])
+        assert bool((res[1] == 1).all())
+        so = split_socks(res[0])
+        for f, (lo, size, w) in enumerate(((A_OFF, A_SIZE, wa), (B_OFF, B_SIZE, wb))):
+            assert [int(so[f][k]) for k in so.dtype.names] == [(seq[f] + 300) % G, (w + 300) % size, size - 300, 300, 3, 0, f, 3 * (f + 1)]
+            data = np.frombuffer(b"".join(s[54:] for s in segs[f]), dtype=np.uint8)
+            first = min(300, size - w)
+            for at, piece in ((lo + w, data[:first]), (lo, data[first:])):
+                if piece.size == 0:
+                    continue
+                w0, w1 = max(0, at - MARGIN), min(big.numel(), at + piece.size + MARGIN)
+                written.append((at, piece))
+                want = np.full(w1 - w0, FILL, dtype=np.uint8)
+                for x, p in written:  # (an earlier call's bytes may lie in this window)
+                    a, b = max(x, w0), min(x + p.size, w1)
+                    if a < b:
+                        want[a - w0 : b - w0] = p[a - x : b - x]
+                got = big[w0:w1].cpu().numpy()
+                bad = np.flatnonzero(got != want)
+                assert bad.size == 0, f"call {call}, ring {f}: {bad.size} bytes differ around {at}, first at {w0 + int(bad[0])}"
+            seq[f] += 300
+    written = [(at, at + p.size) for at, p in written]
+    assert any(a < G < b for a, b in written) and any(a == A_OFF for a, _ in written) and any(b == big.numel() for _, b in written)
+    assert any(b == A_OFF + A_SIZE for _, b in written)
+    for a, b in written:  # what was written (and compared above) back to FILL: the whole tensor holds it again
+        big[a:b].fill_(FILL)
+    for c0 in range(0, big.numel(), 1 << 28):
+        assert bool((big[c0 : c0 + (1 << 28)] == FILL).all()), f"a byte of {c0}..{c0 + (1 << 28)} outside the writes was written"
 
 
 @functools.lru_cache(maxsize=None)
