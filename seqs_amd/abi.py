@@ -72,6 +72,13 @@ SOCK_OUT_DTYPE = np.dtype([("rcv_nxt", "<u4"), ("ring_wpos", "<u4"), ("ring_free
                            ("n_delivered", "<u4"), ("n_dropped", "<u4"), ("flow", "<u4"), ("stop", "<u4")])
 DELIVER_MAX_SOCKS = 65536
 NO_FLOW = 0xFFFFFFFF  # fs_rx_sock_out.flow / .stop of a socket without a flow in the batch
+# fs_rx_snd: one socket's send side for the receive call (8 bytes), and fs_rx_snd_out (32 bytes, no padding)
+SND_DTYPE = np.dtype([("snd_una", "<u4"), ("snd_wnd", "<u4")])
+SND_OUT_DTYPE = np.dtype([("snd_una", "<u4"), ("snd_wnd", "<u4"), ("n_taken", "<u4"), ("n_dup", "<u4"), ("n_unsent", "<u4"),
+                          ("n_rejected", "<u4"), ("n_keepalive", "<u4"), ("flags", "<u4")])
+RECV_ACK_OWED, RECV_FIN = 1, 2  # fs_rx_snd_out.flags
+# the per-frame codes of the receive call
+RECV_NONE, RECV_TAKEN, RECV_DUPLICATE, RECV_UNSENT, RECV_REJECTED, RECV_KEEPALIVE, RECV_RING_FULL = range(7)
 # fs_tx_sock: one socket of the ring send (104 bytes, no padding), and fs_tx_sock_out (32 bytes)
 TX_SOCK_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("ring_off", "<u8"), ("ring_size", "<u4"),
                           ("ring_rpos", "<u4"), ("ring_buffered", "<u4"), ("snd_una", "<u4"), ("snd_nxt", "<u4"),
@@ -162,6 +169,15 @@ SEND_RINGS_PROTOTYPES = {
     "fs_send_rings_batch_host": (_st, [_p, _p, _u32, _p, _u64, _u32, _u32, _u32, _p, _u64, _p, _p, _p, _p, _p]),
 }
 
+# The functions include/framesum_recv.h declares (the fourth header), in its order: product symbols too.
+# The delivery's prototypes with `snd`, `snd_out` and `code` behind `delivered`.
+RECV_PROTOTYPES = {
+    "fs_recv_flows_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p, _p, _u64, _p, _p,
+                                  _p, _p, _p, _p, _p, _p]),
+    "fs_recv_flows_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p, _p, _u64,
+                                       _p, _p, _p, _p, _p, _p, _p]),
+}
+
 # Not in the header, set only where the loaded library has them: the test library's hooks
 # (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
 OPTIONAL_PROTOTYPES = {
@@ -197,7 +213,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     if not os.path.exists(p):
         raise FramesumError(f"{p} is missing — run __graft_entry__.build() (or make -C seqs_amd/csrc)")
     lib = ctypes.CDLL(p)
-    tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **OPTIONAL_PROTOTYPES}
+    tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **RECV_PROTOTYPES, **OPTIONAL_PROTOTYPES}
     for name, (restype, argtypes) in tables.items():
         if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
             continue

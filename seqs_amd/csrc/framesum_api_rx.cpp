@@ -2,7 +2,9 @@
 // fs_coalesce_batch_host (kernels: framesum_coalesce.hip), fs_coalesce_flows_batch and
 // fs_coalesce_flows_batch_host (framesum_flows.hip), and what their host forms share -- and
 // (include/framesum_deliver.h) the delivery into socket rings behind the second family:
-// fs_deliver_flows_batch and fs_deliver_flows_batch_host (framesum_deliver.hip).
+// fs_deliver_flows_batch and fs_deliver_flows_batch_host (framesum_deliver.hip), and
+// (include/framesum_recv.h) the receive call behind the delivery: fs_recv_flows_batch and
+// fs_recv_flows_batch_host (framesum_recv.hip).
 #include <algorithm>
 #include <array>
 #include <cstring>
@@ -12,6 +14,7 @@
 #include "framesum_ctx.h"
 #include "framesum_deliver.h"
 #include "framesum_flows.h"
+#include "framesum_recv.h"
 
 using namespace framesum::host;
 
@@ -279,13 +282,15 @@ static fs_status deliver_check(fs_ctx* ctx, const char* fn, const void* frames, 
 
 // The launches of a checked device-resident delivery call on `stream`: the flow call's (or its zero
 // totals for an empty batch), `delivered` zeroed, the socket block staged in a block of its own, the
-// delivery kernels. `d_copied`: as coalesce_enqueue's (non-empty batches only).
+// delivery kernels. `d_copied`: as coalesce_enqueue's (non-empty batches only). `layout` (nullable):
+// flows_enqueue's, for the receive call's launches behind these.
 static fs_status deliver_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
                                  uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
                                  const std::vector<uint32_t>& table, uint8_t* rings, fs_rx_sock_out* socks_out,
                                  uint8_t* delivered, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
                                  fs_rx_flow* flows, uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals,
-                                 fs_digest* out, uint8_t* status, hipStream_t stream, const uint8_t** d_copied = nullptr) {
+                                 fs_digest* out, uint8_t* status, hipStream_t stream, const uint8_t** d_copied = nullptr,
+                                 framesum::FlowScratch* layout = nullptr) {
     framesum::FlowScratch fs{};
     if (n == 0) {
         FS_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(fs_rx_flow_totals), stream));
@@ -295,6 +300,7 @@ static fs_status deliver_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint6
         if (st != FS_SUCCESS) return st;
         if (delivered) FS_HIP(ctx, hipMemsetAsync(delivered, 0, n, stream));
     }
+    if (layout) *layout = fs;
     if (n_socks == 0) return FS_SUCCESS;
     const dl::Block b = dl::block_of(n_socks);
     const framesum::DeliverScratch ds = framesum::deliver_scratch(n, n_socks);
@@ -336,6 +342,120 @@ fs_status fs_deliver_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint6
                            reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- The receive call (fs_recv_flows_batch / fs_recv_flows_batch_host, include/framesum_recv.h): the
+// delivery, and behind it the fold of every listed socket's ACKs and windows (framesum_recv.hip) ----
+
+namespace rv = framesum::recv;
+
+// What the receive call adds to the delivery's arguments.
+struct RecvPart {
+    const fs_rx_snd* snd;
+    fs_rx_snd_out* snd_out;
+    uint8_t* code;
+};
+
+static fs_status recv_check(fs_ctx* ctx, const char* fn, const fs_rx_sock* socks, uint32_t n_socks, const RecvPart& rp) {
+    const rv::CheckSnd c = rv::check_snd(socks, rp.snd, n_socks, rp.snd_out != nullptr);
+    if (c.bad != rv::kSndGood)
+        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": socket " + std::to_string(c.sock) + ": " + rv::bad_snd_text(c.bad));
+    return FS_SUCCESS;
+}
+
+// The launches of a checked device-resident receive call on `stream`: deliver_enqueue's, `code`
+// zeroed, the send-side block staged in a block of its own, the receive kernels.
+static fs_status recv_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
+                              uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
+                              const std::vector<uint32_t>& table, uint8_t* rings, fs_rx_sock_out* socks_out,
+                              uint8_t* delivered, const RecvPart& rp, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
+                              fs_rx_flow* flows, uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out,
+                              uint8_t* status, hipStream_t stream, const uint8_t** d_copied = nullptr) {
+    framesum::FlowScratch fs{};
+    fs_status st = deliver_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, socks, n_socks, table, rings, socks_out,
+                                   delivered, payload, payload_cap, runs, flows, order, run_of, totals, out, status, stream,
+                                   d_copied, &fs);
+    if (st != FS_SUCCESS) return st;
+    if (rp.code && n != 0) FS_HIP(ctx, hipMemsetAsync(rp.code, 0, n, stream));
+    if (n_socks == 0) return FS_SUCCESS;
+    const framesum::RecvScratch rs = framesum::recv_scratch(n);
+    st = ctx->rv_scratch.grow(ctx, rs.bytes);
+    if (st != FS_SUCCESS) return st;
+    const uint64_t block_bytes = (uint64_t)n_socks * sizeof(rv::Sock);
+    SegStage* sg = nullptr;
+    st = stage_block(ctx, block_bytes, &sg);
+    if (st != FS_SUCCESS) return st;
+    rv::stage(socks, rp.snd, n_socks, reinterpret_cast<rv::Sock*>(sg->h));
+    FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, block_bytes, hipMemcpyHostToDevice, stream));
+    sg->used = true;  // (from here on the block may be read by queued work)
+    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
+    const hipError_t le = framesum::launch_recv(frames, offsets, n, ctx->fl_scratch.p, fs, ctx->dl_scratch.p,
+                                                framesum::deliver_scratch(n, n_socks), socks_out, sg->d, n_socks, rp.snd_out,
+                                                rp.code, ctx->rv_scratch.p, rs, wgs, stream);
+    const hipError_t re = hipEventRecord(sg->done, stream);
+    if (le != hipSuccess) return hip_err(ctx, le, "fs_recv_flows_batch: launch");
+    if (re != hipSuccess) return hip_err(ctx, re, "hipEventRecord(sg->done, stream)");
+    return FS_SUCCESS;
+}
+
+// The host form of the delivery (`rp` null) and of the receive call, behind their checks.
+static fs_status deliver_host(fs_ctx* ctx, const char* fn, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                              const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks,
+                              uint32_t n_socks, const std::vector<uint32_t>& table, const dl::Check& c, uint8_t* rings,
+                              fs_rx_sock_out* socks_out, uint8_t* delivered, const RecvPart* rp, uint8_t* payload,
+                              uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
+                              fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
+    if (n == 0) {  // nothing for a device to do: the sockets keep their state
+        std::memset(totals, 0, sizeof(fs_rx_flow_totals));
+        for (uint32_t s = 0; s < n_socks; ++s) socks_out[s] = dl::untouched(socks[s]);
+        for (uint32_t s = 0; rp && s < n_socks; ++s) rp->snd_out[s] = rv::untouched(rp->snd[s].snd_una, rp->snd[s].snd_wnd);
+        return FS_SUCCESS;
+    }
+    // the device's socks_out (and snd_out behind it) and the rings' span (the kernels address ring bytes
+    // at base + ring_off)
+    const uint64_t span = c.hi - c.lo;
+    const uint64_t at_snd_out = (uint64_t)n_socks * sizeof(fs_rx_sock_out);
+    fs_status st = begin_host_call(ctx);
+    if (st == FS_SUCCESS) st = ctx->dl_arrays.grow(ctx, at_snd_out + (rp ? (uint64_t)n_socks * sizeof(fs_rx_snd_out) : 0));
+    if (st == FS_SUCCESS) st = ctx->dl_rings.grow(ctx, span);
+    if (st != FS_SUCCESS) return st;
+    fs_rx_sock_out* d_socks_out = ctx->dl_arrays.as<fs_rx_sock_out>();
+    fs_rx_snd_out* d_snd_out = ctx->dl_arrays.as<fs_rx_snd_out>(at_snd_out);
+    uint8_t* d_rings = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ctx->dl_rings.p) - c.lo);
+    // behind the runs, per frame: a flow (32), order (4), run_of (4), delivered (1), code (1, the receive call)
+    const uint64_t at_order = (uint64_t)n * 32, at_run_of = (uint64_t)n * 36, at_delivered = (uint64_t)n * 40,
+                   at_code = (uint64_t)n * 41;
+    return rx_host(
+        ctx, fn, frames, frames_bytes, offsets, lengths, n, payload, payload_cap, runs, totals, out, status, ctx->fl_arrays,
+        rp ? 42 : 41,
+        [&](const Staged& s, uint64_t d_cap, fs_rx_run* d_runs, uint8_t* d_rest, fs_rx_flow_totals* d_totals,
+            const uint8_t** d_copied) {
+            // the span goes in first, so that the copy back returns the caller's own bytes between the rings
+            if (span != 0) FS_HIP(ctx, hipMemcpyAsync(ctx->dl_rings.p, rings + c.lo, span, hipMemcpyHostToDevice, s.ks));
+            uint8_t* d_delivered = delivered ? d_rest + at_delivered : nullptr;
+            fs_rx_flow* d_flows = flows ? reinterpret_cast<fs_rx_flow*>(d_rest) : nullptr;
+            uint32_t* d_order = reinterpret_cast<uint32_t*>(d_rest + at_order);
+            uint32_t* d_run_of = run_of ? reinterpret_cast<uint32_t*>(d_rest + at_run_of) : nullptr;
+            if (!rp)
+                return deliver_enqueue(ctx, s.base, s.d_off, s.d_len, n, mtu, flags, socks, n_socks, table, d_rings, d_socks_out,
+                                       d_delivered, ctx->co_payload.p, d_cap, d_runs, d_flows, d_order, d_run_of, d_totals,
+                                       s.d_out, s.d_st, s.ks, d_copied);
+            const RecvPart d_rp{rp->snd, d_snd_out, rp->code ? d_rest + at_code : nullptr};
+            return recv_enqueue(ctx, s.base, s.d_off, s.d_len, n, mtu, flags, socks, n_socks, table, d_rings, d_socks_out,
+                                d_delivered, d_rp, ctx->co_payload.p, d_cap, d_runs, d_flows, d_order, d_run_of, d_totals,
+                                s.d_out, s.d_st, s.ks, d_copied);
+        },
+        [&](const fs_rx_flow_totals& t) { return t.n_accepted <= n && t.n_runs <= t.n_accepted && t.n_flows <= t.n_runs; },
+        [&](const fs_rx_flow_totals& t, const uint8_t* d_rest) {
+            return std::array<D2H, 8>{{{flows, d_rest, (uint64_t)t.n_flows * sizeof(fs_rx_flow)},
+                                       {order, d_rest + at_order, (uint64_t)t.n_accepted * 4},
+                                       {run_of, d_rest + at_run_of, (uint64_t)n * 4},
+                                       {delivered, d_rest + at_delivered, (uint64_t)n},
+                                       {n_socks ? rings + c.lo : nullptr, ctx->dl_rings.p, span},
+                                       {socks_out, d_socks_out, (uint64_t)n_socks * sizeof(fs_rx_sock_out)},
+                                       {rp ? rp->snd_out : nullptr, d_snd_out, (uint64_t)n_socks * sizeof(fs_rx_snd_out)},
+                                       {rp ? rp->code : nullptr, d_rest + at_code, (uint64_t)n}}};
+        });
+}
+
 fs_status fs_deliver_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
                                       const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags,
                                       const fs_rx_sock* socks, uint32_t n_socks, uint8_t* rings, uint64_t rings_bytes,
@@ -350,41 +470,49 @@ fs_status fs_deliver_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64
     const fs_status ast = deliver_check(ctx, fn, frames, offsets, lengths, n, flags, socks, n_socks, rings, rings_bytes,
                                         socks_out, payload, payload_cap, runs, order, totals, false, table, c);
     if (ast != FS_SUCCESS) return ast;
-    if (n == 0) {  // nothing for a device to do: the sockets keep their state
-        std::memset(totals, 0, sizeof(fs_rx_flow_totals));
-        for (uint32_t s = 0; s < n_socks; ++s) socks_out[s] = dl::untouched(socks[s]);
-        return FS_SUCCESS;
-    }
-    // the device's socks_out and the rings' span (the kernels address ring bytes at base + ring_off)
-    const uint64_t span = c.hi - c.lo;
-    fs_status st = begin_host_call(ctx);
-    if (st == FS_SUCCESS) st = ctx->dl_arrays.grow(ctx, (uint64_t)n_socks * sizeof(fs_rx_sock_out));
-    if (st == FS_SUCCESS) st = ctx->dl_rings.grow(ctx, span);
+    return deliver_host(ctx, fn, frames, frames_bytes, offsets, lengths, n, mtu, flags, socks, n_socks, table, c, rings,
+                        socks_out, delivered, nullptr, payload, payload_cap, runs, flows, order, run_of, totals, out, status);
+}
+
+fs_status fs_recv_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                              uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
+                              uint8_t* rings, uint64_t rings_bytes, fs_rx_sock_out* socks_out, uint8_t* delivered,
+                              const fs_rx_snd* snd, fs_rx_snd_out* snd_out, uint8_t* code, uint8_t* payload,
+                              uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order,
+                              uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    const char* const fn = "fs_recv_flows_batch";
+    std::vector<uint32_t> table;
+    dl::Check c;
+    const RecvPart rp{snd, snd_out, code};
+    fs_status st = deliver_check(ctx, fn, frames, offsets, lengths, n, flags, socks, n_socks, rings, rings_bytes, socks_out,
+                                 payload, payload_cap, runs, order, totals, true, table, c);
+    if (st == FS_SUCCESS) st = recv_check(ctx, fn, socks, n_socks, rp);
     if (st != FS_SUCCESS) return st;
-    fs_rx_sock_out* d_socks_out = ctx->dl_arrays.as<fs_rx_sock_out>();
-    uint8_t* d_rings = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ctx->dl_rings.p) - c.lo);
-    // behind the runs, per frame: a flow (32), order (4), run_of (4), delivered (1)
-    const uint64_t at_order = (uint64_t)n * 32, at_run_of = (uint64_t)n * 36, at_delivered = (uint64_t)n * 40;
-    return rx_host(
-        ctx, fn, frames, frames_bytes, offsets, lengths, n, payload, payload_cap, runs, totals, out, status, ctx->fl_arrays, 41,
-        [&](const Staged& s, uint64_t d_cap, fs_rx_run* d_runs, uint8_t* d_rest, fs_rx_flow_totals* d_totals,
-            const uint8_t** d_copied) {
-            // the span goes in first, so that the copy back returns the caller's own bytes between the rings
-            if (span != 0) FS_HIP(ctx, hipMemcpyAsync(ctx->dl_rings.p, rings + c.lo, span, hipMemcpyHostToDevice, s.ks));
-            return deliver_enqueue(ctx, s.base, s.d_off, s.d_len, n, mtu, flags, socks, n_socks, table, d_rings, d_socks_out,
-                                   delivered ? d_rest + at_delivered : nullptr, ctx->co_payload.p, d_cap, d_runs,
-                                   flows ? reinterpret_cast<fs_rx_flow*>(d_rest) : nullptr,
-                                   reinterpret_cast<uint32_t*>(d_rest + at_order),
-                                   run_of ? reinterpret_cast<uint32_t*>(d_rest + at_run_of) : nullptr, d_totals, s.d_out,
-                                   s.d_st, s.ks, d_copied);
-        },
-        [&](const fs_rx_flow_totals& t) { return t.n_accepted <= n && t.n_runs <= t.n_accepted && t.n_flows <= t.n_runs; },
-        [&](const fs_rx_flow_totals& t, const uint8_t* d_rest) {
-            return std::array<D2H, 6>{{{flows, d_rest, (uint64_t)t.n_flows * sizeof(fs_rx_flow)},
-                                       {order, d_rest + at_order, (uint64_t)t.n_accepted * 4},
-                                       {run_of, d_rest + at_run_of, (uint64_t)n * 4},
-                                       {delivered, d_rest + at_delivered, (uint64_t)n},
-                                       {n_socks ? rings + c.lo : nullptr, ctx->dl_rings.p, span},
-                                       {socks_out, d_socks_out, (uint64_t)n_socks * sizeof(fs_rx_sock_out)}}};
-        });
+    FS_HIP(ctx, hipSetDevice(ctx->device));
+    return recv_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, socks, n_socks, table, rings, socks_out, delivered, rp,
+                        payload, payload_cap, runs, flows, order, run_of, totals, out, status,
+                        reinterpret_cast<hipStream_t>(stream));
+}
+
+fs_status fs_recv_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                                   const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags,
+                                   const fs_rx_sock* socks, uint32_t n_socks, uint8_t* rings, uint64_t rings_bytes,
+                                   fs_rx_sock_out* socks_out, uint8_t* delivered, const fs_rx_snd* snd,
+                                   fs_rx_snd_out* snd_out, uint8_t* code, uint8_t* payload, uint64_t payload_cap,
+                                   fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
+                                   fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    const char* const fn = "fs_recv_flows_batch_host";
+    std::vector<uint32_t> table;
+    dl::Check c;
+    const RecvPart rp{snd, snd_out, code};
+    fs_status ast = deliver_check(ctx, fn, frames, offsets, lengths, n, flags, socks, n_socks, rings, rings_bytes, socks_out,
+                                  payload, payload_cap, runs, order, totals, false, table, c);
+    if (ast == FS_SUCCESS) ast = recv_check(ctx, fn, socks, n_socks, rp);
+    if (ast != FS_SUCCESS) return ast;
+    return deliver_host(ctx, fn, frames, frames_bytes, offsets, lengths, n, mtu, flags, socks, n_socks, table, c, rings,
+                        socks_out, delivered, &rp, payload, payload_cap, runs, flows, order, run_of, totals, out, status);
 }

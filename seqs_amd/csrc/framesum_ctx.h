@@ -110,6 +110,9 @@ struct fs_ctx {
     // fs_deliver_flows_batch_host (the rings' span; socks_out). Its socket block is staged through
     // seg_stage, like the sends of fs_segment_batch.
     DevBuf dl_scratch, dl_rings, dl_arrays;
+    // the receive call: the kernels' scratch. fs_recv_flows_batch_host keeps snd_out behind socks_out
+    // in dl_arrays; the call's block is staged through seg_stage like the delivery's.
+    DevBuf rv_scratch;
     std::string err;
 };
 

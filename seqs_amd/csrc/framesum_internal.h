@@ -8,6 +8,7 @@
 
 #include "../../include/framesum.h"
 #include "../../include/framesum_deliver.h"
+#include "../../include/framesum_recv.h"
 #include "framesum_choice.h"
 
 namespace framesum {
@@ -144,5 +145,20 @@ hipError_t launch_deliver(const uint8_t* frames, const uint64_t* offsets, uint32
                           const FlowScratch& fs, const fs_rx_flow_totals* totals, const uint8_t* d_block, uint32_t n_socks,
                           uint32_t hash_mask, uint8_t* rings, fs_rx_sock_out* socks_out, uint8_t* delivered,
                           uint8_t* scratch, const DeliverScratch& s, int max_workgroups, hipStream_t stream);
+
+// ---- The send side of the receive call (framesum_recv.hip). The launches that follow a batch's
+// delivery launches on `stream` (fs_recv_flows_batch in include/framesum_recv.h) and read what those
+// left in `flow_scratch` (laid out as `fs`), in `deliver_scratch` (laid out as `ds`) and in `socks_out`.
+// `d_block`: the device copy of the staged block (framesum_recv.h stage: one Sock per socket).
+// `scratch`: recv_scratch(n).bytes of device memory, 8-byte aligned. `code` is nullable, and zeroed by
+// the caller. With n of 0 only the sockets' out records are written. `max_workgroups` caps every grid.
+struct RecvScratch {
+    uint64_t aw, bytes;
+};
+RecvScratch recv_scratch(uint32_t n);
+hipError_t launch_recv(const uint8_t* frames, const uint64_t* offsets, uint32_t n, const uint8_t* flow_scratch,
+                       const FlowScratch& fs, const uint8_t* deliver_scratch, const DeliverScratch& ds,
+                       const fs_rx_sock_out* socks_out, const uint8_t* d_block, uint32_t n_socks, fs_rx_snd_out* snd_out,
+                       uint8_t* code, uint8_t* scratch, const RecvScratch& s, int max_workgroups, hipStream_t stream);
 
 }  // namespace framesum

@@ -23,9 +23,10 @@ import numpy as np
 from .abi import (  # noqa: F401 (re-exported: this module is the binding's public face)
     DELIVER_MAX_SOCKS, DELIVER_PROTOTYPES, DIGEST_DTYPE, EXPORTED_SYMBOLS, FCS_APPEND, FILL_CSUM, FLOW_DTYPE,
     FLOW_TOTALS_DTYPE, FS_E_HIP, FS_E_INVALID, FS_E_NODEVICE, FS_E_NOMEM, FS_ERR_FCS, FS_SUCCESS, NO_FLOW, NO_RUN,
-    PROTOTYPES, RUN_DTYPE, RX_FCS, SEGMENT_MAX_FRAMES, SEND_DTYPE, SEND_MAX_SOCKS, SEND_NONE, SEND_RINGS_PROTOTYPES,
-    SOCK_DTYPE, SOCK_OUT_DTYPE, TEST_LIB_PATH, TOTALS_DTYPE, TX_ACK, TX_FIN, TX_PSH, TX_SOCK_DTYPE, TX_SOCK_OUT_DTYPE,
-    VERDICTS, FramesumError, lib_path, load_library, sock_key,
+    PROTOTYPES, RECV_ACK_OWED, RECV_DUPLICATE, RECV_FIN, RECV_KEEPALIVE, RECV_NONE, RECV_PROTOTYPES, RECV_REJECTED,
+    RECV_RING_FULL, RECV_TAKEN, RECV_UNSENT, RUN_DTYPE, RX_FCS, SEGMENT_MAX_FRAMES, SEND_DTYPE, SEND_MAX_SOCKS, SEND_NONE,
+    SEND_RINGS_PROTOTYPES, SND_DTYPE, SND_OUT_DTYPE, SOCK_DTYPE, SOCK_OUT_DTYPE, TEST_LIB_PATH, TOTALS_DTYPE, TX_ACK, TX_FIN,
+    TX_PSH, TX_SOCK_DTYPE, TX_SOCK_OUT_DTYPE, VERDICTS, FramesumError, lib_path, load_library, sock_key,
 )
 
 _vp, _u64 = ctypes.c_void_p, ctypes.c_uint64
@@ -81,6 +82,7 @@ _RX = ("fs_coalesce_batch", TOTALS_DTYPE, ())
 _RX_FLOWS = ("fs_coalesce_flows_batch", FLOW_TOTALS_DTYPE,
              ((FLOW_DTYPE, "n_flows"), (np.dtype(np.uint32), "n_accepted")))
 _RX_DELIVER = ("fs_deliver_flows_batch", *_RX_FLOWS[1:])
+_RX_RECV = ("fs_recv_flows_batch", *_RX_FLOWS[1:])  # (the delivery call with snd, snd_out and code behind delivered)
 
 
 @dataclass
@@ -504,6 +506,55 @@ class Engine(_Handle):
                 _array_ptr(marks) if delivered else None)
         return (socks_out, marks, *self._rx_host(_RX_DELIVER, frames, offsets, lengths, mtu, flags, payload, args))
 
+    # ---- the receive call: the delivery plus each socket's ACKs and windows (include/framesum_recv.h) ----
+    def recv_flows_device(self, frames, offsets, lengths, socks: np.ndarray, snd: np.ndarray, rings, mtu: int = 0,
+                          flags: int = 0, payload=None, delivered: bool = True, code: bool = True, stream=None):
+        """deliver_flows_device plus, for every listed socket, what ControlBlock.Recv does to the send
+        side of an Established connection for each frame of its flow (fs_recv_flows_batch): `snd` is a
+        SND_DTYPE array on the host, parallel to `socks` (snd.UNA and snd.WND before the batch). Returns
+        (snd_out, code, then deliver_flows_device's tuple) device tensors: snd_out (n_socks, 32) uint8 =
+        SND_OUT_DTYPE records (snd.UNA and snd.WND after the batch, the counts per code, RECV_ACK_OWED |
+        RECV_FIN), code (n,) uint8 (RECV_TAKEN .. RECV_RING_FULL for the frames of a listed socket's
+        flow before its stop, RECV_NONE otherwise; None when `code` is False). Asynchronous on `stream`;
+        split_snd() brings snd_out to the host."""
+        import torch
+
+        socks = np.ascontiguousarray(socks, dtype=SOCK_DTYPE)
+        snd = np.ascontiguousarray(snd, dtype=SND_DTYPE)
+        assert snd.size == socks.size, "one send-side record per socket"
+        n, dev = int(lengths.numel()), frames.device
+        assert rings.is_cuda and rings.dtype == torch.uint8 and rings.is_contiguous()
+        socks_out = torch.empty((int(socks.size), SOCK_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        snd_out = torch.empty((int(socks.size), SND_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        marks = torch.empty((n,), dtype=torch.uint8, device=dev) if delivered else None
+        codes = torch.empty((n,), dtype=torch.uint8, device=dev) if code else None
+        args = (_array_ptr(socks), int(socks.size), _tensor_ptr(rings), rings.numel(), _tensor_ptr(socks_out),
+                _tensor_ptr(marks) if delivered else None, _array_ptr(snd), _tensor_ptr(snd_out),
+                _tensor_ptr(codes) if code else None)
+        return (snd_out, codes, socks_out, marks,
+                *self._rx_device(_RX_RECV, frames, offsets, lengths, mtu, flags, payload, stream, args))
+
+    def recv_flows_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, socks: np.ndarray,
+                        snd: np.ndarray, rings: np.ndarray, mtu: int = 0, flags: int = 0, payload=None,
+                        delivered: bool = True, code: bool = True):
+        """recv_flows_device from and to host memory (fs_recv_flows_batch_host). Returns (snd_out
+        SND_OUT_DTYPE[n_socks], code uint8[n] or None, then deliver_flows_host's tuple)."""
+        socks = np.ascontiguousarray(socks, dtype=SOCK_DTYPE)
+        snd = np.ascontiguousarray(snd, dtype=SND_DTYPE)
+        assert snd.size == socks.size, "one send-side record per socket"
+        assert isinstance(rings, np.ndarray) and rings.dtype == np.uint8 and rings.flags["C_CONTIGUOUS"]
+        assert rings.flags["WRITEABLE"], "recv_flows_host writes into `rings`"
+        n = int(np.asarray(lengths).size)
+        socks_out = np.zeros(int(socks.size), dtype=SOCK_OUT_DTYPE)
+        snd_out = np.zeros(int(socks.size), dtype=SND_OUT_DTYPE)
+        marks = np.zeros(n, dtype=np.uint8) if delivered else None
+        codes = np.zeros(n, dtype=np.uint8) if code else None
+        args = (_array_ptr(socks), int(socks.size), _array_ptr(rings), rings.nbytes, _array_ptr(socks_out),
+                _array_ptr(marks) if delivered else None, _array_ptr(snd), _array_ptr(snd_out),
+                _array_ptr(codes) if code else None)
+        return (snd_out, codes, socks_out, marks,
+                *self._rx_host(_RX_RECV, frames, offsets, lengths, mtu, flags, payload, args))
+
     # ---- TCP segments from socket TX rings (include/framesum_send.h) ------------
     @staticmethod
     def send_rings_layout(socks: np.ndarray, flags: int = 0, align: int = 1):
@@ -699,12 +750,14 @@ def send_rings_layout(socks: np.ndarray, flags: int = 0, align: int = 1):
     return int(n.value), int(nbytes.value), socks_out
 
 
-def tx_sock_from(sock_out, tx=None, **fields) -> np.ndarray:
+def tx_sock_from(sock_out, tx=None, snd_out=None, **fields) -> np.ndarray:
     """TX_SOCK_DTYPE record(s) whose receive side is what a delivery left: rcv_nxt and rcv_wnd (=
     ring_free, the room of the RX ring) come from `sock_out`, the SOCK_OUT_DTYPE record(s) of
     deliver_flows_device / deliver_flows_host. `tx`: the record(s) to start from (the socket's
     template, TX ring and send state), else zeros; `fields` set further fields, e.g. flags=TX_ACK
-    for the ACK that answers the delivery."""
+    for the ACK that answers the delivery. `snd_out`: the SND_OUT_DTYPE record(s) of recv_flows_device
+    / recv_flows_host for the same sockets; snd_una and snd_wnd then come from them, and TX_ACK is
+    or-ed into flags where RECV_ACK_OWED is set."""
     sock_out = np.atleast_1d(np.asarray(sock_out, dtype=SOCK_OUT_DTYPE))
     res = np.zeros(sock_out.size, dtype=TX_SOCK_DTYPE) if tx is None else \
         np.atleast_1d(np.array(tx, dtype=TX_SOCK_DTYPE, copy=True))
@@ -712,6 +765,11 @@ def tx_sock_from(sock_out, tx=None, **fields) -> np.ndarray:
     res["rcv_nxt"], res["rcv_wnd"] = sock_out["rcv_nxt"], sock_out["ring_free"]
     for name, value in fields.items():
         res[name] = value
+    if snd_out is not None:
+        snd_out = np.atleast_1d(np.asarray(snd_out, dtype=SND_OUT_DTYPE))
+        assert res.size == snd_out.size, "one TX record per receive record"
+        res["snd_una"], res["snd_wnd"] = snd_out["snd_una"], snd_out["snd_wnd"]
+        res["flags"] |= np.where(snd_out["flags"] & RECV_ACK_OWED, TX_ACK, 0).astype(np.uint32)
     return res
 
 
@@ -740,6 +798,11 @@ def split_flows(runs, flows, order, totals):
 def split_socks(socks_out) -> np.ndarray:
     """The host view of deliver_flows_device's `socks_out` tensor (this waits for it): SOCK_OUT_DTYPE[n_socks]."""
     return _records(socks_out, SOCK_OUT_DTYPE)
+
+
+def split_snd(snd_out) -> np.ndarray:
+    """The host view of recv_flows_device's `snd_out` tensor (this waits for it): SND_OUT_DTYPE[n_socks]."""
+    return _records(snd_out, SND_OUT_DTYPE)
 
 
 def shard_count(n: int, nshards: int, shard: int) -> int:
