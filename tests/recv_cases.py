@@ -274,3 +274,180 @@ def round_trip():
     fr = [frame(hdrs[0], 500, 995, ACK, 60), frame(hdrs[1], 500, 990, ACK, 60), frame(hdrs[2], 500, 992, ACK | PSH, 30, data(rng, 8))]
     socks = dref.socks_of(*[dref.sock(dref.key_of_header(h), 500, 1 + 65 * f, 64, snd_nxt=1000) for f, h in enumerate(hdrs)])
     return RCase(fref.finish(fr), socks, ref.snd_of((990, 0), (990, 0), (990, 0)), 200, hdrs=hdrs)
+
+
+# ==== the edge suite (tests/test_gpu_recv_edges.py) ===============================================
+# What the walk carries from one round of four chunks to the next, a chunk full of constants, the half
+# point where the first suite has none, a payload length above 2^15, and frames that are not slots.
+
+# ---- a. state that changes in every chunk of rounds 2 to 5 ---------------------------------------
+
+LONG_POSITIONS = (255, 256, 257, 319, 320, 383, 384, 447, 448, 511, 512, 513, 575, 576, 767, 768, 769, 1023, 1024, 1029)
+LONG_LANE_FLOWS = [(1030, code, LONG_POSITIONS) for code in range(1, 7)]
+
+
+def round_and_chunk(slot):
+    """(round, chunk) of a flow's slot as recv_walk walks it: rounds of 256 slots counted from 1, four
+    chunks of 64 in each."""
+    return slot // 256 + 1, slot % 256 // 64
+
+
+# ---- b. four long flows in one workgroup ---------------------------------------------------------
+
+FOUR_FLOWS = ((1030, 5, LONG_POSITIONS), (522, 3, None), (321, 6, None), (70, 1, None))
+
+
+@functools.lru_cache(maxsize=None)
+def four_long_flows():
+    """Lane flows of 1030, 522, 321 and 70 frames and of four codes, interleaved, one socket each in
+    flow order: the four waves of the first workgroup walk 5, 3, 2 and 1 rounds. info['mine'][g]: the
+    batch indices of flow g's frames."""
+    parts = [lane_flow(*spec) for spec in FOUR_FLOWS]
+    where = fref.interleave([range(len(p.frames)) for p in parts])
+    socks = []
+    for g, p in enumerate(parts):
+        s = p.socks.copy()
+        s["ring_off"] = 3 + 4100 * g
+        socks.append(s)
+    mine = [[i for i, (h, _) in enumerate(where) if h == g] for g in range(len(parts))]
+    return RCase([parts[g].frames[k] for g, k in where], dref.socks_of(*socks), np.concatenate([p.snd for p in parts]),
+                 3 + 4100 * len(parts) + 2, mine=mine, parts=parts)
+
+
+# ---- c. a chunk of 64 constants ------------------------------------------------------------------
+
+DENSE = (64, 48)
+
+
+@functools.lru_cache(maxsize=None)
+def dense_constants(dense=64, seed=6800):
+    """150 frames of one flow. Slots 0 to dense - 1: admitted 1-byte data segments with ACK (constants
+    of the scan), their Acks drawn from [snd_nxt - 900, snd_nxt] in no order, so that snd.UNA jumps
+    forwards and backwards from lane to lane. From slot `dense` on three pure ACKs and a data segment in
+    turn, each pure ACK a few bytes on either side of the running snd.UNA (half of a chunk's newer, half
+    not, the first one newer): a lane that saw another snd.UNA would give another code. With 64 the
+    snd.UNA behind 64 constants is carried into the next chunk; with 48 the lanes 48 to 63 meet 48 and
+    more constants below them in their own chunk. Every frame has a window of its own."""
+    rng = np.random.default_rng(seed + dense)
+    hdr = fref.flow_header(rng, 0x6800 + dense)
+    snd_nxt, rcv_nxt = 0x3000, M32 - 30
+    una0 = snd_nxt - 500
+    una, nxt, frames, windows = una0, rcv_nxt, [], [int(w) for w in rng.permutation(60000)[:150] + 1]
+    newer = {}
+    for lo, hi in ((dense, 64), (64, 128), (128, 150)):
+        pure = [k for k in range(lo, hi) if k % 4 != 3]
+        flip = [bool(f) for f in rng.permutation(len(pure)) % 2 == 0]
+        if pure and not flip[0]:
+            first = flip.index(True)
+            flip[0], flip[first] = True, False
+        newer.update(zip(pure, flip))
+    for k in range(150):
+        if k < dense or k % 4 == 3:
+            una = snd_nxt - int(rng.integers(0 if k < dense - 1 else 50, 901))
+            frames.append(frame(hdr, nxt, una, ACK | PSH, windows[k], data(rng, 1)))
+            nxt += 1
+        elif newer[k]:
+            una += int(rng.integers(1, 6))
+            frames.append(frame(hdr, nxt, una, ACK, windows[k]))
+        else:
+            frames.append(frame(hdr, nxt, una - int(rng.integers(0, 6)), ACK, windows[k]))
+    return one_socket(hdr, frames, rcv_nxt, snd_nxt, una0, windows=windows, una=una, dense=dense)
+
+
+# ---- d. half points ------------------------------------------------------------------------------
+
+HALF_SMALL = ["data at the half point", "no pure half point"]
+
+
+@functools.lru_cache(maxsize=None)
+def half_small(name):
+    """Admitted data segments whose Ack is exactly 2^31 behind snd_nxt: rule (c) passes them, they are
+    taken and leave snd.UNA at that distance. With a pure ACK at the half point among them the chunk is
+    stepped; without one the scan itself meets a snd.UNA 2^31 behind. Pinned by hand."""
+    rng = np.random.default_rng(6810 + HALF_SMALL.index(name))
+    hdr = fref.flow_header(rng, 0x6810 + HALF_SMALL.index(name))
+    fr = [frame(hdr, 500, 1000 - HALF, ACK, 11, data(rng, 4)), frame(hdr, 504, 1000, ACK, 12),
+          frame(hdr, 504, 1000 - HALF, ACK, 13, data(rng, 4)), frame(hdr, 508, 1000 - HALF, ACK, 14),
+          frame(hdr, 508, 1000 - HALF - 1, ACK, 15, data(rng, 4)), frame(hdr, 508, 5, ACK, 16)]
+    if name == "data at the half point":
+        return one_socket(hdr, fr, 500, 1000, 1000, codes=[1, 1, 1, 2, 3, 1], delivered=[1, 0, 1, 0, 2, 0],
+                          snd_out=(5, 16, 4, 1, 1, 0, 0, ref.ACK_OWED))
+    # frame 4 one byte inside the half (newer than a snd.UNA 2^31 behind), frame 6 at snd_nxt
+    fr[3], fr[5] = frame(hdr, 508, 1000 - HALF + 1, ACK, 14), frame(hdr, 508, 1000, ACK, 16)
+    return one_socket(hdr, fr, 500, 1000, 1000, codes=[1, 1, 1, 1, 3, 1], delivered=[1, 0, 1, 0, 2, 0],
+                      snd_out=(1000, 16, 5, 0, 1, 0, 0, ref.ACK_OWED))
+
+
+@functools.lru_cache(maxsize=None)
+def half_long():
+    """400 frames: rising pure ACKs bring snd.UNA to snd_nxt at slot 389; slots 384 to 399 are a chunk
+    of 16 lanes in round 2. Slot 390 is the half point (taken), 393 an admitted data segment with
+    Ack == snd_nxt, 395 the half point again (taken), 396 the same Ack (a duplicate)."""
+    rng = np.random.default_rng(6820)
+    hdr = fref.flow_header(rng, 0x6820)
+    snd_nxt, nxt, fr = 7, 500, []
+    una0 = snd_nxt - 390
+    for k in range(390):
+        fr.append(frame(hdr, nxt, una0 + k + 1, ACK, 100 + k))
+    fr += [frame(hdr, nxt, snd_nxt - HALF, ACK, 490), frame(hdr, nxt, snd_nxt - HALF + 1, ACK, 491),
+           frame(hdr, nxt, snd_nxt - HALF + 2, ACK, 492), frame(hdr, nxt, snd_nxt, ACK | PSH, 493, data(rng, 3)),
+           frame(hdr, nxt + 3, snd_nxt, ACK, 494), frame(hdr, nxt + 3, snd_nxt - HALF, ACK, 495),
+           frame(hdr, nxt + 3, snd_nxt - HALF, ACK, 496)]
+    fr += [frame(hdr, nxt + 3, snd_nxt - HALF + k, ACK, 500 + k) for k in (1, 2, 3)]
+    return one_socket(hdr, fr, 500, snd_nxt, una0, at={390: 1, 393: 1, 395: 1, 396: 2}, una=(snd_nxt - HALF + 3) % M32, wnd=503)
+
+
+# ---- e. payloads above 2^15 ----------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def jumbo():
+    """Five times a data segment of the longest payload RecvEth accepts, a pure ACK at the new rcv.NXT
+    and a keepalive one below it: the length the rcv.NXT scan adds is above 2^15, and rcv.NXT crosses 2^32."""
+    import deliver_cases as dcases
+
+    rng = np.random.default_rng(6830)
+    hdr = fref.flow_header(rng, 0x6830)
+    rcv_nxt, fr = M32 - 100_000, []
+    nxt = rcv_nxt
+    for k in range(5):
+        fr.append(frame(hdr, nxt, 901 + 2 * k, ACK, 50 + k, data(rng, dcases.JUMBO)))
+        nxt += dcases.JUMBO
+        fr += [frame(hdr, nxt, 902 + 2 * k, ACK, 60 + k), frame(hdr, nxt - 1, 1000, ACK, 70 + k)]
+    return one_socket(hdr, fr, rcv_nxt, 1000, 900, ring=400_000, codes=[1, 1, 5] * 5, snd_out=(910, 64, 10, 0, 0, 0, 5, ref.ACK_OWED),
+                      rcv_nxt_out=227_405)
+
+
+# ---- f. frames of the flow that are not slots ----------------------------------------------------
+
+NOT_SLOTS = {"damaged pure ACKs": (63, 64), "a damaged data segment": (10, 63, 64)}
+
+
+def damaged_tcp(f: bytes) -> bytes:
+    """The frame with one bit of its TCP checksum field flipped."""
+    b = bytearray(f)
+    b[14 + 4 * (b[14] & 15) + 16] ^= 0x10
+    return bytes(b)
+
+
+@functools.lru_cache(maxsize=None)
+def not_slots(name):
+    """lane_flow(130, 2) with some of its frames damaged (RecvEth drops them: they are no slots, and
+    every later frame of the flow sits that many lanes lower), interleaved with UDP frames that have
+    the flow's addresses and ports and with a TCP flow that has no socket. info['mine']: the batch
+    indices of the socket's frames, info['foreign']: the others, info['damaged']: indices into mine."""
+    base = lane_flow(130, 2)
+    rng = np.random.default_rng(6840)
+    mine = list(base.frames)
+    for k in NOT_SLOTS[name]:
+        mine[k] = damaged_tcp(mine[k])
+    udp = []
+    for k in range(20):
+        u = bytearray(fref.udp_frame(rng, data(rng, 5 + k)))
+        u[26:38] = mine[0][26:38]  # (IHL 5 in both: the addresses and the ports)
+        udp.append(bytes(u))
+    other = fref.segments(rng, fref.flow_header(rng, 0x6841), 77, [9] * 30)
+    groups = [mine, fref.finish(udp), fref.finish(other)]
+    where = fref.interleave([range(len(g)) for g in groups])
+    return RCase([groups[g][k] for g, k in where], base.socks, base.snd, base.rings_bytes,
+                 mine=[i for i, (g, _) in enumerate(where) if g == 0], foreign=[i for i, (g, _) in enumerate(where) if g != 0],
+                 damaged=NOT_SLOTS[name], base=base)

@@ -499,17 +499,21 @@ def sockets_of_the_flows(case, e):
 
 @gpu
 @pytest.mark.parametrize("fcs", [False, True])
-@pytest.mark.parametrize("call", ["coalesce", "flows", "deliver"])
+@pytest.mark.parametrize("call", ["coalesce", "flows", "deliver", "recv"])
 @pytest.mark.parametrize("which", PLACEMENTS)
 def test_rx_source_beyond_4gib(eng, big, which, call, fcs):
     """The frames read from beyond 2^32: payload with its noise margins, runs, (flows, order,) run_of,
     totals, digests and verdicts against the restatement of the small copy; for the delivery also
-    socks_out, delivered and the whole of a small rings buffer, one socket per TCP flow."""
+    socks_out, delivered and the whole of a small rings buffer, one socket per TCP flow; for the receive
+    call (whose gather forms a 64-bit frame address of its own) also snd_out and code, each socket's
+    snd.UNA 100 behind its snd.NXT."""
     import torch
 
+    import recv_ref as rref
     import test_gpu_coalesce as tc
     import test_gpu_deliver as td
     import test_gpu_flows as tf
+    import test_gpu_recv as tr
 
     flags = cref.RX_FCS if fcs else 0
     for k, case in enumerate(rx_cases(fcs)):
@@ -519,10 +523,15 @@ def test_rx_source_beyond_4gib(eng, big, which, call, fcs):
         e = ref.expected(case.buf, case.off, case.ln, 0, flags, noise, plead, room)
         assert e["n_runs"] >= 2 and e["payload_bytes"] > 0 and (k == 0 or (e["st"] != 0).any())
         ln_dev, noise_dev = dev(case.ln), dev(noise)
-        if call == "deliver":
+        if call in ("deliver", "recv"):
             socks, rings_bytes = sockets_of_the_flows(case, e)
             rings = td.sentinel(rings_bytes, k)
-            e = dref.expected(case.buf, case.off, case.ln, 0, flags, noise, plead, room, socks, rings)
+            if call == "recv":
+                snd = tr.snd_behind(socks)
+                e = rref.expected(case.buf, case.off, case.ln, 0, flags, noise, plead, room, socks, snd, rings)
+                assert int((e["code"] != 0).sum()) == int((e["delivered"] != 0).sum()) and {1, 6} <= {int(c) for c in e["code"]}
+            else:
+                e = dref.expected(case.buf, case.off, case.ln, 0, flags, noise, plead, room, socks, rings)
             assert socks.size == e["n_flows"] >= 2 and (e["delivered"] == 1).any() and (k == 0 or (e["delivered"] == 2).any())
             rings_dev = dev(rings)
         for label, bases in placements(case, big, which):
@@ -540,6 +549,14 @@ def test_rx_source_beyond_4gib(eng, big, which, call, fcs):
                 torch.cuda.synchronize()
                 td.compare_delivery(e, res[0], res[1], rt)
                 tf.compare(e, pt.cpu().numpy(), *res[3:])
+            elif call == "recv":
+                rt = rings_dev.clone()
+                res = eng.recv_flows_device(big, dev(case.off + bases), ln_dev, socks, snd, rt, 0, flags,
+                                            payload=pt[plead : plead + room])
+                torch.cuda.synchronize()
+                tr.compare_recv(e, res[0], res[1])
+                td.compare_delivery(e, res[2], res[3], rt)
+                tf.compare(e, pt.cpu().numpy(), *res[5:])
             else:
                 res = eng.coalesce_flows_device(big, dev(case.off + bases), ln_dev, 0, flags, payload=pt[plead : plead + room])
                 torch.cuda.synchronize()
