@@ -1,12 +1,14 @@
-// framesum C ABI (include/framesum.h) -- the two RX coalesce families: fs_coalesce_batch and
-// fs_coalesce_batch_host (kernels: framesum_coalesce.hip), fs_coalesce_flows_batch and
-// fs_coalesce_flows_batch_host (framesum_flows.hip), and what their host forms share -- and
-// (include/framesum_deliver.h) the delivery into socket rings behind the second family:
-// fs_deliver_flows_batch and fs_deliver_flows_batch_host (framesum_deliver.hip), and
-// (include/framesum_recv.h) the receive call behind the delivery: fs_recv_flows_batch and
-// fs_recv_flows_batch_host (framesum_recv.hip).
+// framesum C ABI -- the four RX call kinds, each with a device form and a host form:
+//   the plain coalesce       fs_coalesce_batch, fs_coalesce_batch_host (include/framesum.h;
+//                            kernels: framesum_coalesce.hip)
+//   the flow-aware coalesce  fs_coalesce_flows_batch, ..._host (framesum_flows.hip)
+//   the delivery             fs_deliver_flows_batch, ..._host (include/framesum_deliver.h;
+//                            framesum_deliver.hip): the flow call, then the delivery into socket rings
+//   the receive call         fs_recv_flows_batch, ..._host (include/framesum_recv.h; framesum_recv.hip):
+//                            the delivery, then the fold of every listed socket's ACKs and windows
+// A call is one record (RxCall) that the entry point fills from its flat arguments; the checks, the
+// stages up to the call's kind and the one host form all read that record.
 #include <algorithm>
-#include <array>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -17,120 +19,272 @@
 #include "framesum_recv.h"
 
 using namespace framesum::host;
+using framesum::RxBatch;
+using framesum::RxLaunch;
+using framesum::RxLeft;
+using framesum::RxResults;
+namespace rxp = framesum::plan::rx;
+namespace dl = framesum::deliver;
+namespace rv = framesum::recv;
 
-// ---- What the two host forms share ----
+namespace {
 
-// One copy back to the caller (skipped when the caller passed no array, or nothing is to come back).
-struct D2H {
-    void* dst;
-    const void* src;
-    uint64_t bytes;
+// The socket part of a delivery or a receive call: the caller's lists, and what check_socks makes of
+// them (the socket table, the span of `rings` the listed rings cover).
+struct RxSocks {
+    const fs_rx_sock* socks = nullptr;
+    const fs_rx_snd* snd = nullptr;
+    uint32_t n_socks = 0;
+    uint64_t rings_bytes = 0;
+    std::vector<uint32_t> table;
+    dl::Check span{};
+};
+// A call as its entry point got it: `fn` names it in the error texts, `r` holds the caller's pointers.
+struct RxCall {
+    rxp::Kind kind;
+    const char* fn;
+    RxBatch b;
+    RxResults r{};
+    RxSocks s;
+    RxCall(rxp::Kind kind_, const char* fn_, const RxBatch& b_) : kind(kind_), fn(fn_), b(b_) {}
+    // the flat arguments, group by group as the ABI lists them
+    void coalesce(uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, void* totals, fs_digest* out,
+                  uint8_t* status) {
+        r.payload = payload, r.payload_cap = payload_cap, r.out = out, r.status = status;
+        r.array[rxp::kRuns] = runs, r.array[rxp::kRunOf] = run_of, r.array[rxp::kTotals] = totals;
+    }
+    void flows(fs_rx_flow* flows, uint32_t* order) { r.array[rxp::kFlowRecs] = flows, r.array[rxp::kOrder] = order; }
+    void sockets(const fs_rx_sock* socks, uint32_t n_socks, uint8_t* rings, uint64_t rings_bytes, fs_rx_sock_out* socks_out,
+                 uint8_t* delivered) {
+        s.socks = socks, s.n_socks = n_socks, s.rings_bytes = rings_bytes, r.rings = rings;
+        r.array[rxp::kSocksOut] = socks_out, r.array[rxp::kDelivered] = delivered;
+    }
+    void send_side(const fs_rx_snd* snd, fs_rx_snd_out* snd_out, uint8_t* code) {
+        s.snd = snd, r.array[rxp::kSndOut] = snd_out, r.array[rxp::kCode] = code;
+    }
+};
+// The call as the launches see it: in the device forms the caller's batch and arrays on the caller's
+// stream, in the host forms the staged batch and the context's device arrays on the compute stream.
+struct RxDevice {
+    RxBatch b;
+    RxResults r;
+    hipStream_t stream;
 };
 
-// A checked host-staged coalesce call `fn` of either family: the batch staged through slot 0, the
-// family's launches (`enqueue`), then what they wrote copied back. The forms differ in the type of
-// their totals, in what lies behind the runs in `arrays` (the device result arrays: the totals, a run
-// per frame, then `rest_per_frame` bytes per frame of the family's own), in whether totals are
-// `consistent`, and in the copies `rest` adds for its own arrays.
-template <class Totals, class Enqueue, class Consistent, class Rest>
-static fs_status rx_host(fs_ctx* ctx, const char* fn, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
-                         const uint32_t* lengths, uint32_t n, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
-                         Totals* totals, fs_digest* out, uint8_t* status, DevBuf& arrays, uint32_t rest_per_frame,
-                         Enqueue enqueue, Consistent consistent, Rest rest) {
-    if (n == 0) {
-        std::memset(totals, 0, sizeof(Totals));
+fs_status invalid(fs_ctx* ctx, const RxCall& c, const std::string& what) {
+    return set_err(ctx, FS_E_INVALID, std::string(c.fn) + ": " + what);
+}
+
+// Every check of a call, none of which needs a device; `aligned`: the device forms' alignment of
+// `frames`. An empty batch needs only `totals` and, in the socket calls, good sockets.
+fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
+    const RxBatch& b = c.b;
+    const bool by_flow = c.kind != rxp::kPlain;
+    if (by_flow && b.n > framesum::flows::kMaxFrames) return invalid(ctx, c, "n too large (at most 2^30 frames per call)");
+    if (b.flags & ~(uint32_t)FS_RX_FCS) return invalid(ctx, c, "flags must be 0 or FS_RX_FCS");
+    if (b.n > kMaxFrames) return invalid(ctx, c, "n too large (at most 2^31 frames per call)");
+    if (!c.r.totals()) return invalid(ctx, c, "null pointer");
+    if (b.n != 0) {
+        if (!b.frames || !b.offsets || !b.lengths || !c.r.runs()) return invalid(ctx, c, "null pointer");
+        if (!c.r.payload && c.r.payload_cap != 0) return invalid(ctx, c, "null payload with a non-zero payload_cap");
+        if (aligned && (reinterpret_cast<uintptr_t>(b.frames) & 3u)) return invalid(ctx, c, "frames must be 4-byte aligned");
+        if (by_flow && !c.r.order()) return invalid(ctx, c, "null pointer");  // (as `runs`)
+    }
+    if (c.kind >= rxp::kDeliver) {  // the socket list's checks (framesum_deliver.h), which also build the table
+        RxSocks& s = c.s;
+        s.span = dl::check_socks(s.socks, s.n_socks, c.r.rings != nullptr, c.r.socks_out() != nullptr, s.rings_bytes,
+                                 ctx->flow_hash_mask, s.table);
+        if (s.span.bad != dl::kGood)
+            return invalid(ctx, c, "socket " + std::to_string(s.span.sock) + ": " + dl::bad_text(s.span.bad));
+    }
+    if (c.kind == rxp::kRecv) {
+        const rv::CheckSnd cs = rv::check_snd(c.s.socks, c.s.snd, c.s.n_socks, c.r.snd_out() != nullptr);
+        if (cs.bad != rv::kSndGood) return invalid(ctx, c, "socket " + std::to_string(cs.sock) + ": " + rv::bad_snd_text(cs.bad));
+    }
+    return FS_SUCCESS;
+}
+
+// ---- The stages of a checked call on the device. Each enqueues on d.stream behind the one before it.
+
+// The cap of the grids behind the digest launch: up to 8 workgroups of 256 lanes per CU unless
+// fs_ctx_set_workgroups caps them.
+int rx_workgroups(const fs_ctx* ctx) { return ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus; }
+
+// `out` and `status` of a device-resident call that passes none: the context's own.
+fs_status spare_results(fs_ctx* ctx, RxDevice& d) {
+    if (d.r.out && d.r.status) return FS_SUCCESS;
+    const fs_status st = ctx->co_results.grow(ctx, (uint64_t)d.b.n * 9);
+    if (st != FS_SUCCESS) return st;
+    if (!d.r.out) d.r.out = ctx->co_results.as<fs_digest>();
+    if (!d.r.status) d.r.status = ctx->co_results.p + (uint64_t)d.b.n * 8;
+    return FS_SUCCESS;
+}
+
+hipError_t digest_launch(fs_ctx* ctx, const RxDevice& d) {
+    return launch(ctx, d.b.frames, d.b.offsets, d.b.lengths, d.b.n, d.b.mtu, d.r.out, d.r.status, d.stream,
+                  (d.b.flags & FS_RX_FCS) ? framesum::FsOp::kFcs : framesum::FsOp::kDigest, nullptr, 0);
+}
+
+// The digest launch and the plain gather of a non-empty batch.
+fs_status plain_stage(fs_ctx* ctx, RxDevice& d, const RxLaunch& how, RxLeft& left) {
+    const framesum::CoScratch s = framesum::coalesce_scratch(d.b.n);
+    fs_status st = ctx->co_scratch.grow(ctx, s.bytes);
+    if (st == FS_SUCCESS) st = spare_results(ctx, d);
+    if (st != FS_SUCCESS) return st;
+    left.copied = ctx->co_scratch.p + s.copied;
+    FS_HIP(ctx, digest_launch(ctx, d));
+    FS_HIP(ctx, framesum::launch_coalesce(d.b, d.r, ctx->co_scratch.p, how));
+    return FS_SUCCESS;
+}
+
+// The digest launch (skipped unless all of the flow launches' steps run: the test library's hook) and
+// the flow gather of a non-empty batch.
+fs_status flows_stage(fs_ctx* ctx, RxDevice& d, const RxLaunch& how, RxLeft& left) {
+    left.fs = framesum::flows_scratch(d.b.n);
+    if (left.fs.sort_bytes == 0)
+        return set_err(ctx, FS_E_HIP, "fs_coalesce_flows_batch: the sort reports no temporary storage size");
+    fs_status st = ctx->fl_scratch.grow(ctx, left.fs.bytes);
+    if (st == FS_SUCCESS) st = spare_results(ctx, d);
+    if (st != FS_SUCCESS) return st;
+    left.flow_scratch = ctx->fl_scratch.p;
+    left.copied = left.flow_scratch + left.fs.copied;
+    if (how.steps == framesum::kFlowStepsAll) FS_HIP(ctx, digest_launch(ctx, d));
+    FS_HIP(ctx, framesum::launch_coalesce_flows(d.b, d.r, left, how));
+    return FS_SUCCESS;
+}
+
+// `delivered` zeroed, the socket block staged in a block of its own, the delivery kernels (which run
+// for an empty batch too: the sockets' out records are written).
+fs_status deliver_stage(fs_ctx* ctx, const RxSocks& s, const RxDevice& d, const RxLaunch& how, RxLeft& left) {
+    if (d.b.n != 0 && d.r.delivered()) FS_HIP(ctx, hipMemsetAsync(d.r.delivered(), 0, d.b.n, d.stream));
+    if (s.n_socks == 0) return FS_SUCCESS;
+    const dl::Block blk = dl::block_of(s.n_socks);
+    left.ds = framesum::deliver_scratch(d.b.n, s.n_socks);
+    const fs_status st = ctx->dl_scratch.grow(ctx, left.ds.bytes);
+    if (st != FS_SUCCESS) return st;
+    left.deliver_scratch = ctx->dl_scratch.p;
+    const auto fill = [&](uint8_t* h_block) {
+        std::memcpy(h_block, s.socks, blk.table);
+        std::memcpy(h_block + blk.table, s.table.data(), 4ull * s.table.size());
+    };
+    const auto kernels = [&](const uint8_t* d_block) { return framesum::launch_deliver(d.b, d.r, left, d_block, s.n_socks, how); };
+    return staged_launch(ctx, blk.bytes, d.stream, "fs_deliver_flows_batch: launch", fill, kernels);
+}
+
+// `code` zeroed, the send-side block staged in a block of its own, the receive kernels.
+fs_status recv_stage(fs_ctx* ctx, const RxSocks& s, const RxDevice& d, const RxLaunch& how, RxLeft& left) {
+    if (d.b.n != 0 && d.r.code()) FS_HIP(ctx, hipMemsetAsync(d.r.code(), 0, d.b.n, d.stream));
+    if (s.n_socks == 0) return FS_SUCCESS;
+    left.rs = framesum::recv_scratch(d.b.n);
+    const fs_status st = ctx->rv_scratch.grow(ctx, left.rs.bytes);
+    if (st != FS_SUCCESS) return st;
+    left.recv_scratch = ctx->rv_scratch.p;
+    const auto fill = [&](uint8_t* h_block) { rv::stage(s.socks, s.snd, s.n_socks, reinterpret_cast<rv::Sock*>(h_block)); };
+    const auto kernels = [&](const uint8_t* d_block) { return framesum::launch_recv(d.b, d.r, left, d_block, s.n_socks, how); };
+    return staged_launch(ctx, (uint64_t)s.n_socks * sizeof(rv::Sock), d.stream, "fs_recv_flows_batch: launch", fill, kernels);
+}
+
+// The stages up to the call's kind. An empty batch has zero totals in place of its gather; the socket
+// calls still run their walks then. `left`: what the stages left (`copied`: non-empty batches only).
+fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
+    const RxLaunch how{rx_workgroups(ctx), ctx->flow_hash_mask, ctx->flow_steps, d.stream};
+    left = RxLeft{};
+    fs_status st = FS_SUCCESS;
+    if (d.b.n == 0)
+        FS_HIP(ctx, hipMemsetAsync(d.r.totals(), 0, rxp::totals_bytes(c.kind), d.stream));
+    else
+        st = c.kind == rxp::kPlain ? plain_stage(ctx, d, how, left) : flows_stage(ctx, d, how, left);
+    if (st == FS_SUCCESS && c.kind >= rxp::kDeliver) st = deliver_stage(ctx, c.s, d, how, left);
+    if (st == FS_SUCCESS && c.kind == rxp::kRecv) st = recv_stage(ctx, c.s, d, how, left);
+    return st;
+}
+
+// A checked device form: the caller's pointers, on the caller's stream.
+fs_status rx_device(fs_ctx* ctx, const RxCall& c, void* stream) {
+    FS_HIP(ctx, hipSetDevice(ctx->device));
+    RxLeft left;
+    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream)}, left);
+}
+
+// A checked host form: the batch staged through slot 0, the result arrays carved from the context's
+// buffer as plan::rx::layout says, the stages, then what they wrote copied back by the same description.
+fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
+    const RxBatch& b = c.b;
+    const RxResults& h = c.r;
+    const RxSocks& s = c.s;
+    const uint32_t n = b.n;
+    const bool sockets = c.kind >= rxp::kDeliver;
+    const uint64_t totals_bytes = rxp::totals_bytes(c.kind);
+    if (n == 0) {  // nothing for a device to do: the sockets keep their state
+        std::memset(h.totals(), 0, totals_bytes);
+        for (uint32_t i = 0; sockets && i < s.n_socks; ++i) h.socks_out()[i] = dl::untouched(s.socks[i]);
+        for (uint32_t i = 0; c.kind == rxp::kRecv && i < s.n_socks; ++i)
+            h.snd_out()[i] = rv::untouched(s.snd[i].snd_una, s.snd[i].snd_wnd);
         return FS_SUCCESS;
     }
-    const framesum::plan::Scan sc = framesum::plan::scan_batch(offsets, lengths, n, frames_bytes);
-    if (sc.bad < n)
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": frame " + std::to_string(sc.bad) + " ends past frames_bytes");
+    const framesum::plan::Scan sc = framesum::plan::scan_batch(b.offsets, b.lengths, n, frames_bytes);
+    if (sc.bad < n) return invalid(ctx, c, "frame " + std::to_string(sc.bad) + " ends past frames_bytes");
     // the device payload buffer: payload_cap, or the most payload the batch can hold when that is less
-    const uint64_t d_cap = std::min(payload_cap, framesum::plan::total_length(lengths, n));
+    const uint64_t d_cap = std::min(h.payload_cap, framesum::plan::total_length(b.lengths, n));
+    // the rings' span (the kernels address ring bytes at base + ring_off)
+    const uint64_t span = s.span.hi - s.span.lo;
+    const rxp::Layout L = rxp::layout(c.kind, n, s.n_socks);
     fs_status st = begin_host_call(ctx);
+    if (st == FS_SUCCESS && sockets) st = ctx->dl_rings.grow(ctx, span);
+    // (the socket calls begin once more, behind the rings' buffer: a second hipSetDevice that keeps their
+    // sequence of HIP calls what profiles/rx_call_refactor/calls.txt compares)
+    if (st == FS_SUCCESS && sockets) st = begin_host_call(ctx);
     if (st == FS_SUCCESS) st = ctx->co_payload.grow(ctx, d_cap);
-    if (st == FS_SUCCESS) st = arrays.grow(ctx, sizeof(Totals) + (uint64_t)n * (sizeof(fs_rx_run) + rest_per_frame));
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, L.bytes);
     if (st != FS_SUCCESS) return st;
-    Staged s;
-    st = stage_batch(ctx, frames, frames_bytes, sc.lo, sc.hi, offsets, lengths, n, s);
+    Staged sg;
+    st = stage_batch(ctx, b.frames, frames_bytes, sc.lo, sc.hi, b.offsets, b.lengths, n, sg);
     if (st != FS_SUCCESS) return st;
-    Totals* d_totals = arrays.as<Totals>();
-    fs_rx_run* d_runs = arrays.as<fs_rx_run>(sizeof(Totals));
-    uint8_t* d_rest = arrays.p + sizeof(Totals) + (uint64_t)n * sizeof(fs_rx_run);
-    const uint8_t* d_copied = nullptr;
-    st = enqueue(s, d_cap, d_runs, d_rest, d_totals, &d_copied);
+    RxDevice d{RxBatch{sg.base, sg.d_off, sg.d_len, n, b.mtu, b.flags}, RxResults{}, sg.ks};
+    d.r.payload = ctx->co_payload.p, d.r.payload_cap = d_cap, d.r.out = sg.d_out, d.r.status = sg.d_st;
+    d.r.rings = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ctx->dl_rings.p) - s.span.lo);
+    // an array the caller did not pass goes to the launches as a null pointer
+    for (uint32_t a = 0; a < rxp::kArrays; ++a) d.r.array[a] = h.array[a] && L.has((rxp::Array)a) ? ctx->rx_arrays.p + L.at[a] : nullptr;
+    // the span goes in first, so that the copy back returns the caller's own bytes between the rings
+    if (span != 0) FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->dl_rings.p, h.rings + s.span.lo, span, hipMemcpyHostToDevice, sg.ks));
+    RxLeft left;
+    st = rx_run(ctx, c, d, left);
     if (st != FS_SUCCESS) {
         drain_host_streams(ctx);
         return st;
     }
     // the totals and how far the payload got written decide what else comes back
-    Totals t;
+    fs_rx_totals plain{};
+    fs_rx_flow_totals by_flow{};
+    void* const t = c.kind == rxp::kPlain ? static_cast<void*>(&plain) : &by_flow;
     uint64_t copied = 0;
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&t, d_totals, sizeof t, hipMemcpyDeviceToHost, s.ks));
-    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&copied, d_copied, 8, hipMemcpyDeviceToHost, s.ks));
-    FS_HIP_DRAIN(ctx, hipStreamSynchronize(s.ks));
-    if (copied > d_cap || !consistent(t)) {
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(t, d.r.totals(), totals_bytes, hipMemcpyDeviceToHost, sg.ks));
+    FS_HIP_DRAIN(ctx, hipMemcpyAsync(&copied, left.copied, 8, hipMemcpyDeviceToHost, sg.ks));
+    FS_HIP_DRAIN(ctx, hipStreamSynchronize(sg.ks));
+    const rxp::Totals got = c.kind == rxp::kPlain ? rxp::Totals{plain.n_runs, 0, 0}
+                                                  : rxp::Totals{by_flow.n_runs, by_flow.n_flows, by_flow.n_accepted};
+    if (copied > d_cap || !rxp::consistent(c.kind, n, got)) {
         drain_host_streams(ctx);
-        return set_err(ctx, FS_E_HIP, std::string(fn) + ": inconsistent totals from the device");
+        return set_err(ctx, FS_E_HIP, std::string(c.fn) + ": inconsistent totals from the device");
     }
-    const auto back = [&](const D2H& c) {
-        return c.dst && c.bytes ? hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s.ks) : hipSuccess;
+    // one copy back to the caller, skipped when the caller passed no array or nothing is to come back
+    const auto back = [&](void* dst, const void* src, uint64_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, sg.ks) : hipSuccess;
     };
-    FS_HIP_DRAIN(ctx, back({payload, ctx->co_payload.p, copied}));
-    FS_HIP_DRAIN(ctx, back({runs, d_runs, (uint64_t)t.n_runs * sizeof(fs_rx_run)}));
-    for (const D2H& c : rest(t, d_rest)) FS_HIP_DRAIN(ctx, back(c));
-    FS_HIP_DRAIN(ctx, back({out, s.d_out, (uint64_t)n * sizeof(fs_digest)}));
-    FS_HIP_DRAIN(ctx, back({status, s.d_st, n}));
-    st = finish_staged(ctx, s);
-    if (st == FS_SUCCESS) *totals = t;
+    FS_HIP_DRAIN(ctx, back(h.payload, ctx->co_payload.p, copied));
+    for (uint32_t a = rxp::kTotals + 1; a < rxp::kArrays; ++a)
+        FS_HIP_DRAIN(ctx, back(h.array[a], d.r.array[a], rxp::bytes_back(c.kind, (rxp::Array)a, n, s.n_socks, got)));
+    FS_HIP_DRAIN(ctx, back(s.n_socks ? h.rings + s.span.lo : nullptr, ctx->dl_rings.p, span));
+    FS_HIP_DRAIN(ctx, back(h.out, sg.d_out, (uint64_t)n * sizeof(fs_digest)));
+    FS_HIP_DRAIN(ctx, back(h.status, sg.d_st, n));
+    st = finish_staged(ctx, sg);
+    if (st == FS_SUCCESS) std::memcpy(h.totals(), t, totals_bytes);
     return st;
 }
 
-// ---- RX coalesce (fs_coalesce_batch / fs_coalesce_batch_host) ----
+}  // namespace
 
-// Every check of a coalesce call, none of which needs a device. An empty batch needs only `totals`.
-static fs_status coalesce_check(fs_ctx* ctx, const char* fn, const void* frames, const void* offsets, const void* lengths,
-                                uint32_t n, uint32_t flags, const void* payload, uint64_t payload_cap, const void* runs,
-                                const void* totals, bool aligned) {
-    if (flags & ~(uint32_t)FS_RX_FCS) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": flags must be 0 or FS_RX_FCS");
-    if (n > kMaxFrames) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": n too large (at most 2^31 frames per call)");
-    if (!totals) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");
-    if (n == 0) return FS_SUCCESS;
-    if (!frames || !offsets || !lengths || !runs) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");
-    if (!payload && payload_cap != 0) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null payload with a non-zero payload_cap");
-    if (aligned && (reinterpret_cast<uintptr_t>(frames) & 3u))
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": frames must be 4-byte aligned");
-    return FS_SUCCESS;
-}
-
-// `out` and `status` of a device-resident call that passes none: the context's own.
-static fs_status spare_results(fs_ctx* ctx, uint32_t n, fs_digest*& out, uint8_t*& status) {
-    if (out && status) return FS_SUCCESS;
-    const fs_status st = ctx->co_results.grow(ctx, (uint64_t)n * 9);
-    if (st != FS_SUCCESS) return st;
-    if (!out) out = ctx->co_results.as<fs_digest>();
-    if (!status) status = ctx->co_results.p + (uint64_t)n * 8;
-    return FS_SUCCESS;
-}
-
-// The digest launch and the coalesce launches of a checked, non-empty device-resident batch on `stream`.
-// `d_copied` (nullable): where on the device the count of written payload bytes lies.
-static fs_status coalesce_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
-                                  uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
-                                  fs_rx_run* runs, uint32_t* run_of, fs_rx_totals* totals, fs_digest* out, uint8_t* status,
-                                  hipStream_t stream, const uint8_t** d_copied = nullptr) {
-    const framesum::CoScratch s = framesum::coalesce_scratch(n);
-    fs_status st = ctx->co_scratch.grow(ctx, s.bytes);
-    if (st == FS_SUCCESS) st = spare_results(ctx, n, out, status);
-    if (st != FS_SUCCESS) return st;
-    if (d_copied) *d_copied = ctx->co_scratch.p + s.copied;
-    FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, stream,
-                       (flags & FS_RX_FCS) ? framesum::FsOp::kFcs : framesum::FsOp::kDigest, nullptr, 0));
-    // up to 8 workgroups of 256 lanes per CU unless fs_ctx_set_workgroups caps the grids
-    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
-    FS_HIP(ctx, framesum::launch_coalesce(frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, run_of,
-                                          totals, ctx->co_scratch.p, wgs, stream));
-    return FS_SUCCESS;
-}
+// ---- The eight entry points: fill the record, check, run.
 
 fs_status fs_coalesce_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
                             uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
@@ -138,16 +292,10 @@ fs_status fs_coalesce_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* 
                             void* stream) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    const fs_status st = coalesce_check(ctx, "fs_coalesce_batch", frames, offsets, lengths, n, flags, payload, payload_cap,
-                                        runs, totals, true);
-    if (st != FS_SUCCESS) return st;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    if (n == 0) {
-        FS_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(fs_rx_totals), reinterpret_cast<hipStream_t>(stream)));
-        return FS_SUCCESS;
-    }
-    return coalesce_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, payload, payload_cap, runs, run_of, totals, out,
-                            status, reinterpret_cast<hipStream_t>(stream));
+    RxCall c(rxp::kPlain, "fs_coalesce_batch", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    const fs_status st = rx_check(ctx, c, true);
+    return st != FS_SUCCESS ? st : rx_device(ctx, c, stream);
 }
 
 fs_status fs_coalesce_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
@@ -156,59 +304,10 @@ fs_status fs_coalesce_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t fr
                                  fs_digest* out, uint8_t* status) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    const char* const fn = "fs_coalesce_batch_host";
-    const fs_status ast =
-        coalesce_check(ctx, fn, frames, offsets, lengths, n, flags, payload, payload_cap, runs, totals, false);
-    if (ast != FS_SUCCESS) return ast;
-    // behind the runs: run_of (4 per frame)
-    return rx_host(
-        ctx, fn, frames, frames_bytes, offsets, lengths, n, payload, payload_cap, runs, totals, out, status, ctx->co_arrays, 4,
-        [&](const Staged& s, uint64_t d_cap, fs_rx_run* d_runs, uint8_t* d_rest, fs_rx_totals* d_totals, const uint8_t** d_copied) {
-            return coalesce_enqueue(ctx, s.base, s.d_off, s.d_len, n, mtu, flags, ctx->co_payload.p, d_cap, d_runs,
-                                    run_of ? reinterpret_cast<uint32_t*>(d_rest) : nullptr, d_totals, s.d_out, s.d_st, s.ks,
-                                    d_copied);
-        },
-        [&](const fs_rx_totals& t) { return t.n_runs <= n; },
-        [&](const fs_rx_totals&, const uint8_t* d_rest) { return std::array<D2H, 1>{{{run_of, d_rest, (uint64_t)n * 4}}}; });
-}
-
-// ---- Flow-aware RX coalesce (fs_coalesce_flows_batch / fs_coalesce_flows_batch_host) ----
-
-static fs_status flows_check(fs_ctx* ctx, const char* fn, const void* frames, const void* offsets, const void* lengths,
-                             uint32_t n, uint32_t flags, const void* payload, uint64_t payload_cap, const void* runs,
-                             const void* order, const void* totals, bool aligned) {
-    if (n > framesum::flows::kMaxFrames)
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": n too large (at most 2^30 frames per call)");
-    const fs_status st =
-        coalesce_check(ctx, fn, frames, offsets, lengths, n, flags, payload, payload_cap, runs, totals, aligned);
-    if (st != FS_SUCCESS) return st;
-    if (n != 0 && !order) return set_err(ctx, FS_E_INVALID, std::string(fn) + ": null pointer");  // (as `runs`)
-    return FS_SUCCESS;
-}
-
-// The digest launch and the flow coalesce launches of a checked, non-empty device-resident batch on
-// `stream`. `d_copied`: as coalesce_enqueue's. `layout` (nullable): where in the context's scratch the
-// launches leave their per-slot arrays, for the delivery launches behind them.
-static fs_status flows_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
-                               uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
-                               fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
-                               fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, hipStream_t stream,
-                               const uint8_t** d_copied = nullptr, framesum::FlowScratch* layout = nullptr) {
-    const framesum::FlowScratch s = framesum::flows_scratch(n);
-    if (layout) *layout = s;
-    if (s.sort_bytes == 0) return set_err(ctx, FS_E_HIP, "fs_coalesce_flows_batch: the sort reports no temporary storage size");
-    fs_status st = ctx->fl_scratch.grow(ctx, s.bytes);
-    if (st == FS_SUCCESS) st = spare_results(ctx, n, out, status);
-    if (st != FS_SUCCESS) return st;
-    if (d_copied) *d_copied = ctx->fl_scratch.p + s.copied;
-    if (ctx->flow_steps == framesum::kFlowStepsAll)
-        FS_HIP(ctx, launch(ctx, frames, offsets, lengths, n, mtu, out, status, stream,
-                           (flags & FS_RX_FCS) ? framesum::FsOp::kFcs : framesum::FsOp::kDigest, nullptr, 0));
-    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
-    FS_HIP(ctx, framesum::launch_coalesce_flows(frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, flows,
-                                                order, run_of, totals, ctx->fl_scratch.p, s, ctx->flow_hash_mask, wgs,
-                                                ctx->flow_steps, stream));
-    return FS_SUCCESS;
+    RxCall c(rxp::kPlain, "fs_coalesce_batch_host", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    const fs_status st = rx_check(ctx, c, false);
+    return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
 }
 
 fs_status fs_coalesce_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
@@ -217,16 +316,11 @@ fs_status fs_coalesce_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint
                                   fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    const fs_status st = flows_check(ctx, "fs_coalesce_flows_batch", frames, offsets, lengths, n, flags, payload,
-                                     payload_cap, runs, order, totals, true);
-    if (st != FS_SUCCESS) return st;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    if (n == 0) {
-        FS_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(fs_rx_flow_totals), reinterpret_cast<hipStream_t>(stream)));
-        return FS_SUCCESS;
-    }
-    return flows_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, payload, payload_cap, runs, flows, order, run_of,
-                         totals, out, status, reinterpret_cast<hipStream_t>(stream));
+    RxCall c(rxp::kFlows, "fs_coalesce_flows_batch", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    const fs_status st = rx_check(ctx, c, true);
+    return st != FS_SUCCESS ? st : rx_device(ctx, c, stream);
 }
 
 fs_status fs_coalesce_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes,
@@ -236,91 +330,11 @@ fs_status fs_coalesce_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint6
                                        fs_digest* out, uint8_t* status) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    const char* const fn = "fs_coalesce_flows_batch_host";
-    const fs_status ast =
-        flows_check(ctx, fn, frames, offsets, lengths, n, flags, payload, payload_cap, runs, order, totals, false);
-    if (ast != FS_SUCCESS) return ast;
-    // behind the runs, per frame: a flow (32), order (4), run_of (4)
-    const uint64_t at_order = (uint64_t)n * 32, at_run_of = (uint64_t)n * 36;
-    return rx_host(
-        ctx, fn, frames, frames_bytes, offsets, lengths, n, payload, payload_cap, runs, totals, out, status, ctx->fl_arrays, 40,
-        [&](const Staged& s, uint64_t d_cap, fs_rx_run* d_runs, uint8_t* d_rest, fs_rx_flow_totals* d_totals,
-            const uint8_t** d_copied) {
-            return flows_enqueue(ctx, s.base, s.d_off, s.d_len, n, mtu, flags, ctx->co_payload.p, d_cap, d_runs,
-                                 flows ? reinterpret_cast<fs_rx_flow*>(d_rest) : nullptr,
-                                 reinterpret_cast<uint32_t*>(d_rest + at_order),
-                                 run_of ? reinterpret_cast<uint32_t*>(d_rest + at_run_of) : nullptr, d_totals, s.d_out, s.d_st,
-                                 s.ks, d_copied);
-        },
-        [&](const fs_rx_flow_totals& t) { return t.n_accepted <= n && t.n_runs <= t.n_accepted && t.n_flows <= t.n_runs; },
-        [&](const fs_rx_flow_totals& t, const uint8_t* d_rest) {
-            return std::array<D2H, 3>{{{flows, d_rest, (uint64_t)t.n_flows * sizeof(fs_rx_flow)},
-                                       {order, d_rest + at_order, (uint64_t)t.n_accepted * 4},
-                                       {run_of, d_rest + at_run_of, (uint64_t)n * 4}}};
-        });
-}
-
-// ---- In-order TCP delivery (fs_deliver_flows_batch / fs_deliver_flows_batch_host, include/framesum_deliver.h) ----
-
-namespace dl = framesum::deliver;
-
-// Every check of a delivery call: the flow call's, then the socket list's (framesum_deliver.h), which
-// also builds the socket table `table` and gives the span of `rings` the listed rings cover.
-static fs_status deliver_check(fs_ctx* ctx, const char* fn, const void* frames, const void* offsets, const void* lengths,
-                               uint32_t n, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks, const void* rings,
-                               uint64_t rings_bytes, const void* socks_out, const void* payload, uint64_t payload_cap,
-                               const void* runs, const void* order, const void* totals, bool aligned,
-                               std::vector<uint32_t>& table, dl::Check& c) {
-    const fs_status st =
-        flows_check(ctx, fn, frames, offsets, lengths, n, flags, payload, payload_cap, runs, order, totals, aligned);
-    if (st != FS_SUCCESS) return st;
-    c = dl::check_socks(socks, n_socks, rings != nullptr, socks_out != nullptr, rings_bytes, ctx->flow_hash_mask, table);
-    if (c.bad != dl::kGood)
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": socket " + std::to_string(c.sock) + ": " + dl::bad_text(c.bad));
-    return FS_SUCCESS;
-}
-
-// The launches of a checked device-resident delivery call on `stream`: the flow call's (or its zero
-// totals for an empty batch), `delivered` zeroed, the socket block staged in a block of its own, the
-// delivery kernels. `d_copied`: as coalesce_enqueue's (non-empty batches only). `layout` (nullable):
-// flows_enqueue's, for the receive call's launches behind these.
-static fs_status deliver_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
-                                 uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
-                                 const std::vector<uint32_t>& table, uint8_t* rings, fs_rx_sock_out* socks_out,
-                                 uint8_t* delivered, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
-                                 fs_rx_flow* flows, uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals,
-                                 fs_digest* out, uint8_t* status, hipStream_t stream, const uint8_t** d_copied = nullptr,
-                                 framesum::FlowScratch* layout = nullptr) {
-    framesum::FlowScratch fs{};
-    if (n == 0) {
-        FS_HIP(ctx, hipMemsetAsync(totals, 0, sizeof(fs_rx_flow_totals), stream));
-    } else {
-        const fs_status st = flows_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, payload, payload_cap, runs, flows,
-                                           order, run_of, totals, out, status, stream, d_copied, &fs);
-        if (st != FS_SUCCESS) return st;
-        if (delivered) FS_HIP(ctx, hipMemsetAsync(delivered, 0, n, stream));
-    }
-    if (layout) *layout = fs;
-    if (n_socks == 0) return FS_SUCCESS;
-    const dl::Block b = dl::block_of(n_socks);
-    const framesum::DeliverScratch ds = framesum::deliver_scratch(n, n_socks);
-    fs_status st = ctx->dl_scratch.grow(ctx, ds.bytes);
-    if (st != FS_SUCCESS) return st;
-    SegStage* sg = nullptr;
-    st = stage_block(ctx, b.bytes, &sg);
-    if (st != FS_SUCCESS) return st;
-    std::memcpy(sg->h, socks, b.table);
-    std::memcpy(sg->h + b.table, table.data(), 4ull * table.size());
-    FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, b.bytes, hipMemcpyHostToDevice, stream));
-    sg->used = true;  // (from here on the block may be read by queued work)
-    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
-    const hipError_t le = framesum::launch_deliver(frames, offsets, n, ctx->fl_scratch.p, fs, totals, sg->d, n_socks,
-                                                   ctx->flow_hash_mask, rings, socks_out, delivered, ctx->dl_scratch.p, ds,
-                                                   wgs, stream);
-    const hipError_t re = hipEventRecord(sg->done, stream);
-    if (le != hipSuccess) return hip_err(ctx, le, "fs_deliver_flows_batch: launch");
-    if (re != hipSuccess) return hip_err(ctx, re, "hipEventRecord(sg->done, stream)");
-    return FS_SUCCESS;
+    RxCall c(rxp::kFlows, "fs_coalesce_flows_batch_host", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    const fs_status st = rx_check(ctx, c, false);
+    return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
 }
 
 fs_status fs_deliver_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
@@ -331,129 +345,12 @@ fs_status fs_deliver_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint6
                                  uint8_t* status, void* stream) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    std::vector<uint32_t> table;
-    dl::Check c;
-    const fs_status st = deliver_check(ctx, "fs_deliver_flows_batch", frames, offsets, lengths, n, flags, socks, n_socks, rings,
-                                       rings_bytes, socks_out, payload, payload_cap, runs, order, totals, true, table, c);
-    if (st != FS_SUCCESS) return st;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    return deliver_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, socks, n_socks, table, rings, socks_out, delivered,
-                           payload, payload_cap, runs, flows, order, run_of, totals, out, status,
-                           reinterpret_cast<hipStream_t>(stream));
-}
-
-// ---- The receive call (fs_recv_flows_batch / fs_recv_flows_batch_host, include/framesum_recv.h): the
-// delivery, and behind it the fold of every listed socket's ACKs and windows (framesum_recv.hip) ----
-
-namespace rv = framesum::recv;
-
-// What the receive call adds to the delivery's arguments.
-struct RecvPart {
-    const fs_rx_snd* snd;
-    fs_rx_snd_out* snd_out;
-    uint8_t* code;
-};
-
-static fs_status recv_check(fs_ctx* ctx, const char* fn, const fs_rx_sock* socks, uint32_t n_socks, const RecvPart& rp) {
-    const rv::CheckSnd c = rv::check_snd(socks, rp.snd, n_socks, rp.snd_out != nullptr);
-    if (c.bad != rv::kSndGood)
-        return set_err(ctx, FS_E_INVALID, std::string(fn) + ": socket " + std::to_string(c.sock) + ": " + rv::bad_snd_text(c.bad));
-    return FS_SUCCESS;
-}
-
-// The launches of a checked device-resident receive call on `stream`: deliver_enqueue's, `code`
-// zeroed, the send-side block staged in a block of its own, the receive kernels.
-static fs_status recv_enqueue(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
-                              uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
-                              const std::vector<uint32_t>& table, uint8_t* rings, fs_rx_sock_out* socks_out,
-                              uint8_t* delivered, const RecvPart& rp, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
-                              fs_rx_flow* flows, uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out,
-                              uint8_t* status, hipStream_t stream, const uint8_t** d_copied = nullptr) {
-    framesum::FlowScratch fs{};
-    fs_status st = deliver_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, socks, n_socks, table, rings, socks_out,
-                                   delivered, payload, payload_cap, runs, flows, order, run_of, totals, out, status, stream,
-                                   d_copied, &fs);
-    if (st != FS_SUCCESS) return st;
-    if (rp.code && n != 0) FS_HIP(ctx, hipMemsetAsync(rp.code, 0, n, stream));
-    if (n_socks == 0) return FS_SUCCESS;
-    const framesum::RecvScratch rs = framesum::recv_scratch(n);
-    st = ctx->rv_scratch.grow(ctx, rs.bytes);
-    if (st != FS_SUCCESS) return st;
-    const uint64_t block_bytes = (uint64_t)n_socks * sizeof(rv::Sock);
-    SegStage* sg = nullptr;
-    st = stage_block(ctx, block_bytes, &sg);
-    if (st != FS_SUCCESS) return st;
-    rv::stage(socks, rp.snd, n_socks, reinterpret_cast<rv::Sock*>(sg->h));
-    FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, block_bytes, hipMemcpyHostToDevice, stream));
-    sg->used = true;  // (from here on the block may be read by queued work)
-    const int wgs = ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus;
-    const hipError_t le = framesum::launch_recv(frames, offsets, n, ctx->fl_scratch.p, fs, ctx->dl_scratch.p,
-                                                framesum::deliver_scratch(n, n_socks), socks_out, sg->d, n_socks, rp.snd_out,
-                                                rp.code, ctx->rv_scratch.p, rs, wgs, stream);
-    const hipError_t re = hipEventRecord(sg->done, stream);
-    if (le != hipSuccess) return hip_err(ctx, le, "fs_recv_flows_batch: launch");
-    if (re != hipSuccess) return hip_err(ctx, re, "hipEventRecord(sg->done, stream)");
-    return FS_SUCCESS;
-}
-
-// The host form of the delivery (`rp` null) and of the receive call, behind their checks.
-static fs_status deliver_host(fs_ctx* ctx, const char* fn, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
-                              const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks,
-                              uint32_t n_socks, const std::vector<uint32_t>& table, const dl::Check& c, uint8_t* rings,
-                              fs_rx_sock_out* socks_out, uint8_t* delivered, const RecvPart* rp, uint8_t* payload,
-                              uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
-                              fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
-    if (n == 0) {  // nothing for a device to do: the sockets keep their state
-        std::memset(totals, 0, sizeof(fs_rx_flow_totals));
-        for (uint32_t s = 0; s < n_socks; ++s) socks_out[s] = dl::untouched(socks[s]);
-        for (uint32_t s = 0; rp && s < n_socks; ++s) rp->snd_out[s] = rv::untouched(rp->snd[s].snd_una, rp->snd[s].snd_wnd);
-        return FS_SUCCESS;
-    }
-    // the device's socks_out (and snd_out behind it) and the rings' span (the kernels address ring bytes
-    // at base + ring_off)
-    const uint64_t span = c.hi - c.lo;
-    const uint64_t at_snd_out = (uint64_t)n_socks * sizeof(fs_rx_sock_out);
-    fs_status st = begin_host_call(ctx);
-    if (st == FS_SUCCESS) st = ctx->dl_arrays.grow(ctx, at_snd_out + (rp ? (uint64_t)n_socks * sizeof(fs_rx_snd_out) : 0));
-    if (st == FS_SUCCESS) st = ctx->dl_rings.grow(ctx, span);
-    if (st != FS_SUCCESS) return st;
-    fs_rx_sock_out* d_socks_out = ctx->dl_arrays.as<fs_rx_sock_out>();
-    fs_rx_snd_out* d_snd_out = ctx->dl_arrays.as<fs_rx_snd_out>(at_snd_out);
-    uint8_t* d_rings = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ctx->dl_rings.p) - c.lo);
-    // behind the runs, per frame: a flow (32), order (4), run_of (4), delivered (1), code (1, the receive call)
-    const uint64_t at_order = (uint64_t)n * 32, at_run_of = (uint64_t)n * 36, at_delivered = (uint64_t)n * 40,
-                   at_code = (uint64_t)n * 41;
-    return rx_host(
-        ctx, fn, frames, frames_bytes, offsets, lengths, n, payload, payload_cap, runs, totals, out, status, ctx->fl_arrays,
-        rp ? 42 : 41,
-        [&](const Staged& s, uint64_t d_cap, fs_rx_run* d_runs, uint8_t* d_rest, fs_rx_flow_totals* d_totals,
-            const uint8_t** d_copied) {
-            // the span goes in first, so that the copy back returns the caller's own bytes between the rings
-            if (span != 0) FS_HIP(ctx, hipMemcpyAsync(ctx->dl_rings.p, rings + c.lo, span, hipMemcpyHostToDevice, s.ks));
-            uint8_t* d_delivered = delivered ? d_rest + at_delivered : nullptr;
-            fs_rx_flow* d_flows = flows ? reinterpret_cast<fs_rx_flow*>(d_rest) : nullptr;
-            uint32_t* d_order = reinterpret_cast<uint32_t*>(d_rest + at_order);
-            uint32_t* d_run_of = run_of ? reinterpret_cast<uint32_t*>(d_rest + at_run_of) : nullptr;
-            if (!rp)
-                return deliver_enqueue(ctx, s.base, s.d_off, s.d_len, n, mtu, flags, socks, n_socks, table, d_rings, d_socks_out,
-                                       d_delivered, ctx->co_payload.p, d_cap, d_runs, d_flows, d_order, d_run_of, d_totals,
-                                       s.d_out, s.d_st, s.ks, d_copied);
-            const RecvPart d_rp{rp->snd, d_snd_out, rp->code ? d_rest + at_code : nullptr};
-            return recv_enqueue(ctx, s.base, s.d_off, s.d_len, n, mtu, flags, socks, n_socks, table, d_rings, d_socks_out,
-                                d_delivered, d_rp, ctx->co_payload.p, d_cap, d_runs, d_flows, d_order, d_run_of, d_totals,
-                                s.d_out, s.d_st, s.ks, d_copied);
-        },
-        [&](const fs_rx_flow_totals& t) { return t.n_accepted <= n && t.n_runs <= t.n_accepted && t.n_flows <= t.n_runs; },
-        [&](const fs_rx_flow_totals& t, const uint8_t* d_rest) {
-            return std::array<D2H, 8>{{{flows, d_rest, (uint64_t)t.n_flows * sizeof(fs_rx_flow)},
-                                       {order, d_rest + at_order, (uint64_t)t.n_accepted * 4},
-                                       {run_of, d_rest + at_run_of, (uint64_t)n * 4},
-                                       {delivered, d_rest + at_delivered, (uint64_t)n},
-                                       {n_socks ? rings + c.lo : nullptr, ctx->dl_rings.p, span},
-                                       {socks_out, d_socks_out, (uint64_t)n_socks * sizeof(fs_rx_sock_out)},
-                                       {rp ? rp->snd_out : nullptr, d_snd_out, (uint64_t)n_socks * sizeof(fs_rx_snd_out)},
-                                       {rp ? rp->code : nullptr, d_rest + at_code, (uint64_t)n}}};
-        });
+    RxCall c(rxp::kDeliver, "fs_deliver_flows_batch", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    const fs_status st = rx_check(ctx, c, true);
+    return st != FS_SUCCESS ? st : rx_device(ctx, c, stream);
 }
 
 fs_status fs_deliver_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
@@ -464,14 +361,12 @@ fs_status fs_deliver_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64
                                       uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    const char* const fn = "fs_deliver_flows_batch_host";
-    std::vector<uint32_t> table;
-    dl::Check c;
-    const fs_status ast = deliver_check(ctx, fn, frames, offsets, lengths, n, flags, socks, n_socks, rings, rings_bytes,
-                                        socks_out, payload, payload_cap, runs, order, totals, false, table, c);
-    if (ast != FS_SUCCESS) return ast;
-    return deliver_host(ctx, fn, frames, frames_bytes, offsets, lengths, n, mtu, flags, socks, n_socks, table, c, rings,
-                        socks_out, delivered, nullptr, payload, payload_cap, runs, flows, order, run_of, totals, out, status);
+    RxCall c(rxp::kDeliver, "fs_deliver_flows_batch_host", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    const fs_status st = rx_check(ctx, c, false);
+    return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
 }
 
 fs_status fs_recv_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
@@ -482,18 +377,13 @@ fs_status fs_recv_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t
                               uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    const char* const fn = "fs_recv_flows_batch";
-    std::vector<uint32_t> table;
-    dl::Check c;
-    const RecvPart rp{snd, snd_out, code};
-    fs_status st = deliver_check(ctx, fn, frames, offsets, lengths, n, flags, socks, n_socks, rings, rings_bytes, socks_out,
-                                 payload, payload_cap, runs, order, totals, true, table, c);
-    if (st == FS_SUCCESS) st = recv_check(ctx, fn, socks, n_socks, rp);
-    if (st != FS_SUCCESS) return st;
-    FS_HIP(ctx, hipSetDevice(ctx->device));
-    return recv_enqueue(ctx, frames, offsets, lengths, n, mtu, flags, socks, n_socks, table, rings, socks_out, delivered, rp,
-                        payload, payload_cap, runs, flows, order, run_of, totals, out, status,
-                        reinterpret_cast<hipStream_t>(stream));
+    RxCall c(rxp::kRecv, "fs_recv_flows_batch", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    const fs_status st = rx_check(ctx, c, true);
+    return st != FS_SUCCESS ? st : rx_device(ctx, c, stream);
 }
 
 fs_status fs_recv_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
@@ -505,14 +395,11 @@ fs_status fs_recv_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t 
                                    fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
     if (!ctx) return FS_E_INVALID;
     ctx->err.clear();
-    const char* const fn = "fs_recv_flows_batch_host";
-    std::vector<uint32_t> table;
-    dl::Check c;
-    const RecvPart rp{snd, snd_out, code};
-    fs_status ast = deliver_check(ctx, fn, frames, offsets, lengths, n, flags, socks, n_socks, rings, rings_bytes, socks_out,
-                                  payload, payload_cap, runs, order, totals, false, table, c);
-    if (ast == FS_SUCCESS) ast = recv_check(ctx, fn, socks, n_socks, rp);
-    if (ast != FS_SUCCESS) return ast;
-    return deliver_host(ctx, fn, frames, frames_bytes, offsets, lengths, n, mtu, flags, socks, n_socks, table, c, rings,
-                        socks_out, delivered, &rp, payload, payload_cap, runs, flows, order, run_of, totals, out, status);
+    RxCall c(rxp::kRecv, "fs_recv_flows_batch_host", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    const fs_status st = rx_check(ctx, c, false);
+    return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
 }

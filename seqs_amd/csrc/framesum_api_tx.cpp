@@ -83,19 +83,9 @@ fs_status framesum::host::tx_enqueue(fs_ctx* ctx, uint64_t block_bytes, const st
                                      hipStream_t stream) {
     const fs_status tst = seg_tables(ctx);
     if (tst != FS_SUCCESS) return tst;
-    SegStage* sg = nullptr;
-    const fs_status st = stage_block(ctx, block_bytes, &sg);
-    if (st != FS_SUCCESS) return st;
-    fill(sg->h);
-    FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, block_bytes, hipMemcpyHostToDevice, stream));
     // two workgroups per CU (their tables fit its LDS twice) unless fs_ctx_set_workgroups caps the grid
     const int wgs = ctx->workgroups > 0 && ctx->workgroups < 2 * ctx->num_cus ? ctx->workgroups : 2 * ctx->num_cus;
-    sg->used = true;  // (from here on the block may be read by queued work)
-    const hipError_t le = launch(sg->d, wgs);
-    const hipError_t re = hipEventRecord(sg->done, stream);
-    if (le != hipSuccess) return hip_err(ctx, le, launch_what);
-    if (re != hipSuccess) return hip_err(ctx, re, "hipEventRecord(sg->done, stream)");
-    return FS_SUCCESS;
+    return staged_launch(ctx, block_bytes, stream, launch_what, fill, [&](const uint8_t* d_block) { return launch(d_block, wgs); });
 }
 
 fs_status framesum::host::tx_host_call(fs_ctx* ctx, const uint8_t* src, uint64_t lo, uint64_t hi, uint64_t n,

@@ -107,14 +107,11 @@ CoScratch coalesce_scratch(uint32_t n) {
     return s;
 }
 
-hipError_t launch_coalesce(const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
-                           uint32_t flags, const uint8_t* status, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
-                           uint32_t* run_of, fs_rx_totals* totals, uint8_t* scratch, int max_workgroups,
-                           hipStream_t stream) {
+hipError_t launch_coalesce(const RxBatch& b, const RxResults& r, uint8_t* scratch, const RxLaunch& how) {
     CoArgs a;
-    const GatherGrids g = fill_gather_args(a, frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, run_of,
-                                           scratch, coalesce_scratch(n), max_workgroups);
-    a.totals = totals;
+    const GatherGrids g = fill_gather_args(a, b, r, scratch, coalesce_scratch(b.n), how.max_workgroups);
+    const hipStream_t stream = how.stream;
+    a.totals = static_cast<fs_rx_totals*>(r.totals());
     hipLaunchKernelGGL(coalesce_classify, dim3(g.scan), dim3(kThreads), 0, stream, a);
     hipLaunchKernelGGL(coalesce_scan_partials, dim3(1), dim3(kThreads), 0, stream, a);
     hipLaunchKernelGGL(coalesce_apply, dim3(g.scan), dim3(kThreads), 0, stream, a);

@@ -3,13 +3,17 @@
 // alignment, a frame's header load and classification, the payload copy by 16 lanes, and the four
 // gather steps -- classify, the scan of the partials, apply, copy -- written once over a mode that
 // each file supplies, with the launch arguments and the scratch layout the two families have in
-// common. (framesum_tx_dev.h takes Piece, load_at and store_at from here.) HIP only; the
+// common; and what the kernels behind the flow launches share (framesum_deliver.hip,
+// framesum_recv.hip): their view of those launches' scratch. (framesum_tx_dev.h takes Piece, load_at
+// and store_at from here.) HIP only; the
 // arithmetic these call is in framesum_coalesce.h, which compiles without HIP.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/framesum.h"
 #include "framesum_coalesce.h"
+#include "framesum_flows.h"
+#include "framesum_internal.h"
 
 namespace framesum {
 namespace codev {
@@ -296,13 +300,12 @@ struct GatherGrids {
     uint32_t scan, copy;
 };
 template <typename A, typename S>
-GatherGrids fill_gather_args(A& a, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
-                             uint32_t flags, const uint8_t* status, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
-                             uint32_t* run_of, uint8_t* scratch, const S& s, int max_workgroups) {
-    a.frames = frames;
-    a.offsets = offsets;
-    a.lengths = lengths;
-    a.status = status;
+GatherGrids fill_gather_args(A& a, const RxBatch& b, const RxResults& r, uint8_t* scratch, const S& s, int max_workgroups) {
+    const uint32_t n = b.n;
+    a.frames = b.frames;
+    a.offsets = b.offsets;
+    a.lengths = b.lengths;
+    a.status = r.status;
     a.rec = reinterpret_cast<uint2*>(scratch + s.rec);
     a.payoff = reinterpret_cast<uint64_t*>(scratch + s.payoff);
     a.partial = reinterpret_cast<decltype(a.partial)>(scratch + s.partial);
@@ -310,13 +313,13 @@ GatherGrids fill_gather_args(A& a, const uint8_t* frames, const uint64_t* offset
     a.copied = reinterpret_cast<unsigned long long*>(scratch + s.copied);
     a.runidx = reinterpret_cast<uint32_t*>(scratch + s.runidx);
     a.hidx = reinterpret_cast<uint32_t*>(scratch + s.hidx);
-    a.payload = payload;
-    a.cap = payload_cap;
-    a.runs = runs;
-    a.run_of = run_of;
+    a.payload = r.payload;
+    a.cap = r.payload_cap;
+    a.runs = r.runs();
+    a.run_of = r.run_of();
     a.n = n;
     a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
-    a.fcs = (flags & FS_RX_FCS) ? 4u : 0u;
+    a.fcs = (b.flags & FS_RX_FCS) ? 4u : 0u;
     const uint32_t cap = (uint32_t)(max_workgroups > 0 ? max_workgroups : 1);
     const uint32_t n_tiles = (uint32_t)(((uint64_t)n + kTileFrames - 1) / kTileFrames);
     return GatherGrids{a.n_blocks < cap ? a.n_blocks : cap, n_tiles < cap ? n_tiles : cap};
@@ -340,6 +343,28 @@ uint64_t lay_run_arrays(S& s, uint64_t at, uint64_t n) {
     s.runidx = at, at += 4ull * n;
     s.hidx = at, at += 4ull * n;
     return at;
+}
+
+// ---- What the kernels behind the flow launches share (framesum_deliver.hip, framesum_recv.hip): the
+// view of what those launches left in their scratch of the same call. Their argument structs derive
+// from it.
+struct FlowView {
+    const uint64_t* sorted;   // per slot: the sort key, whose low b bits are the frame
+    const uint2* rec;         // per slot
+    const uint4* keys;        // per frame
+    const uint32_t* flowidx;  // per slot
+    uint32_t b;
+};
+inline FlowView flow_view(const RxLeft& left, uint32_t n) {
+    return FlowView{reinterpret_cast<const uint64_t*>(left.flow_scratch + left.fs.sorted),
+                    reinterpret_cast<const uint2*>(left.flow_scratch + left.fs.rec),
+                    reinterpret_cast<const uint4*>(left.flow_scratch + left.fs.keys),
+                    reinterpret_cast<const uint32_t*>(left.flow_scratch + left.fs.flowidx), flows::index_bits(n)};
+}
+__device__ __forceinline__ uint32_t slot_frame(const FlowView& v, uint32_t k) { return flows::sort_index(v.sorted[k], v.b); }
+// Lane `l`'s value, l the same in all lanes.
+__device__ __forceinline__ uint32_t lane_value(uint32_t v, uint32_t l) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane((int)l));
 }
 
 }  // namespace codev

@@ -1,7 +1,9 @@
 // Internal to the host side of the C ABI (framesum_api.cpp: context lifecycle, digest and fill calls;
-// framesum_api_tx.cpp: the TX frame build; framesum_api_rx.cpp: the two RX coalesce families): the
-// context, the error helpers and macros, the grow-only device buffer, and the staging helpers of the
-// host-staged calls that stage one batch through slot 0. Defined in framesum_api.cpp.
+// framesum_api_tx.cpp: the TX frame build; framesum_api_rx.cpp: the four RX call kinds -- the plain and
+// the flow-aware coalesce, the delivery into socket rings and the receive call): the context, the error
+// helpers and macros, the grow-only device buffer, the staging blocks and the launch behind one, and the
+// staging helpers of the host-staged calls that stage one batch through slot 0. Defined in
+// framesum_api.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -97,21 +99,20 @@ struct fs_ctx {
     SegStage seg_stage[kSegStages];
     int seg_next = 0;  // the block to wait for when all are busy
     DevBuf seg_payload, seg_frames, seg_arrays;
-    // RX coalesce: the kernels' scratch, out / status when the caller passes none, and the device
-    // buffers of fs_coalesce_batch_host (payload; totals, runs and run_of)
-    DevBuf co_scratch, co_results, co_payload, co_arrays;
-    // flow-aware RX coalesce: the kernels' scratch and the device result arrays of
-    // fs_coalesce_flows_batch_host (out / status and the payload share the buffers above). The hash
-    // mask and the steps are all ones / all steps unless the test library's setters change them.
-    DevBuf fl_scratch, fl_arrays;
+    // The RX calls. The plain coalesce: the kernels' scratch, and out / status when the caller passes
+    // none. The four host forms share the device payload and one buffer of result arrays, laid out per
+    // call by plan::rx::layout (framesum_plan.h).
+    DevBuf co_scratch, co_results, co_payload, rx_arrays;
+    // flow-aware RX coalesce: the kernels' scratch. The hash mask and the steps are all ones / all
+    // steps unless the test library's setters change them.
+    DevBuf fl_scratch;
     uint32_t flow_hash_mask = 0xFFFFFFFFu;
     uint32_t flow_steps = framesum::kFlowStepsAll;
-    // in-order TCP delivery: the kernels' scratch, and the device buffers of
-    // fs_deliver_flows_batch_host (the rings' span; socks_out). Its socket block is staged through
-    // seg_stage, like the sends of fs_segment_batch.
-    DevBuf dl_scratch, dl_rings, dl_arrays;
-    // the receive call: the kernels' scratch. fs_recv_flows_batch_host keeps snd_out behind socks_out
-    // in dl_arrays; the call's block is staged through seg_stage like the delivery's.
+    // in-order TCP delivery: the kernels' scratch, and the rings' span of the host forms. Its socket
+    // block is staged through seg_stage, like the sends of fs_segment_batch.
+    DevBuf dl_scratch, dl_rings;
+    // the receive call: the kernels' scratch; the call's block is staged through seg_stage like the
+    // delivery's.
     DevBuf rv_scratch;
     std::string err;
 };
@@ -153,9 +154,29 @@ void drain_host_streams(fs_ctx* ctx);
     } while (0)
 
 // A staging block (fs_ctx::seg_stage) of at least `bytes` bytes whose previous kernel has ended; the
-// caller fills `h`, copies it to `d`, sets `used` and records `done` behind its last reader.
-// framesum_api_tx.cpp.
+// caller fills `h`, copies it to `d`, sets `used` and records `done` behind its last reader
+// (staged_launch below). framesum_api_tx.cpp.
 fs_status stage_block(fs_ctx* ctx, uint64_t bytes, SegStage** out);
+// One staged block and the launches that read it (the TX frame builds, the delivery, the receive call):
+// a block of `bytes` bytes that `fill(h_block)` fills, its copy to the device on `stream`, the launches
+// `launch(d_block)` starts behind it on the device copy, and the block's event behind them, recorded
+// even when the launch failed (the block may be read by what did get queued). `launch_what` names a
+// failed launch in the error text, which comes before the event's. Nothing is allocated.
+template <class Fill, class Launch>
+fs_status staged_launch(fs_ctx* ctx, uint64_t bytes, hipStream_t stream, const char* launch_what, const Fill& fill,
+                        const Launch& launch) {
+    SegStage* sg = nullptr;
+    const fs_status st = stage_block(ctx, bytes, &sg);
+    if (st != FS_SUCCESS) return st;
+    fill(sg->h);
+    FS_HIP(ctx, hipMemcpyAsync(sg->d, sg->h, bytes, hipMemcpyHostToDevice, stream));
+    sg->used = true;  // (from here on the block may be read by queued work)
+    const hipError_t le = launch(static_cast<const uint8_t*>(sg->d));
+    const hipError_t re = hipEventRecord(sg->done, stream);
+    if (le != hipSuccess) return hip_err(ctx, le, launch_what);
+    if (re != hipSuccess) return hip_err(ctx, re, "hipEventRecord(sg->done, stream)");
+    return FS_SUCCESS;
+}
 // fs_ctx::d_seg_tables, built and uploaded on the first call of a frame-building kernel
 // (fs_segment_batch, fs_send_rings_batch). framesum_api_tx.cpp.
 fs_status seg_tables(fs_ctx* ctx);
@@ -172,11 +193,10 @@ struct TxDevice {
     uint8_t* status;
     hipStream_t stream;
 };
-// What such a call enqueues on `stream` for a checked batch: the tables, a staging block of `block_bytes`
-// bytes that `fill` fills, its copy to the device, the one kernel that `launch` starts on the device
-// copy with at most `workgroups` workgroups, and the block's event behind it. `launch_what` names a
-// failed launch in the error text. (Pass the callables by std::ref: nothing is allocated then.)
-// framesum_api_tx.cpp.
+// What such a call enqueues on `stream` for a checked batch: the tables, then staged_launch of a block
+// of `block_bytes` bytes that `fill` fills and of the one kernel that `launch` starts on the device copy
+// with at most `workgroups` workgroups. `launch_what` names a failed launch in the error text. (Pass
+// the callables by std::ref: nothing is allocated then.) framesum_api_tx.cpp.
 fs_status tx_enqueue(fs_ctx* ctx, uint64_t block_bytes, const std::function<void(uint8_t* h_block)>& fill,
                      const std::function<hipError_t(const uint8_t* d_block, int workgroups)>& launch,
                      const char* launch_what, hipStream_t stream);
@@ -199,7 +219,7 @@ hipError_t launch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, c
 fs_status ensure_slot(fs_ctx* ctx, HostSlot& sl, uint64_t frame_bytes, uint32_t n);
 
 // A host-staged call that stages its whole batch through slot 0 and runs on the compute stream `ks`
-// (fs_fill_batch_host and the two RX coalesce host calls): where the batch lies on the device. The
+// (fs_fill_batch_host and the four RX host forms): where the batch lies on the device. The
 // kernels address frame i at base + offsets[i]: base = staging - cpy_lo (4-B aligned).
 struct Staged {
     HostSlot* sl;

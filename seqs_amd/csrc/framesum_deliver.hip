@@ -39,14 +39,9 @@ namespace {
 using namespace codev;
 namespace dl = deliver;
 
-struct DlArgs {
+struct DlArgs : FlowView {  // (the flow launches' scratch of this call)
     const uint8_t* frames;
     const uint64_t* offsets;
-    // the flow launches' scratch of this call
-    const uint64_t* sorted;   // per slot: the sort key, whose low b bits are the frame
-    const uint2* rec;         // per slot
-    const uint4* keys;        // per frame
-    const uint32_t* flowidx;  // per slot
     const fs_rx_flow_totals* totals;
     // the staged block
     const fs_rx_sock* socks;
@@ -59,10 +54,9 @@ struct DlArgs {
     uint8_t* rings;
     fs_rx_sock_out* socks_out;
     uint8_t* delivered;
-    uint32_t n, n_blocks, n_socks, tmask, hash_mask, b;
+    uint32_t n, n_blocks, n_socks, tmask, hash_mask;
 };
 
-__device__ __forceinline__ uint32_t slot_frame(const DlArgs& a, uint32_t k) { return flows::sort_index(a.sorted[k], a.b); }
 __device__ __forceinline__ uint32_t be32_at(const uint8_t* p) { return __builtin_bswap32(load_at<uint32_t>(p)); }
 
 __global__ void __launch_bounds__(kThreads) deliver_match(const DlArgs a) {
@@ -119,10 +113,6 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t v, WaveScan::storage_type
     uint32_t out;
     WaveScan().inclusive_scan(v, out, storage);
     return out;
-}
-// Lane `l`'s value, l the same in all lanes.
-__device__ __forceinline__ uint32_t lane_value(uint32_t v, uint32_t l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane((int)l));
 }
 __device__ __forceinline__ unsigned long long lanes_below(uint32_t l) { return l >= 64u ? ~0ull : (1ull << l) - 1ull; }
 
@@ -272,34 +262,32 @@ DeliverScratch deliver_scratch(uint32_t n, uint32_t n_socks) {
     return s;
 }
 
-hipError_t launch_deliver(const uint8_t* frames, const uint64_t* offsets, uint32_t n, const uint8_t* flow_scratch,
-                          const FlowScratch& fs, const fs_rx_flow_totals* totals, const uint8_t* d_block, uint32_t n_socks,
-                          uint32_t hash_mask, uint8_t* rings, fs_rx_sock_out* socks_out, uint8_t* delivered,
-                          uint8_t* scratch, const DeliverScratch& s, int max_workgroups, hipStream_t stream) {
+hipError_t launch_deliver(const RxBatch& b, const RxResults& r, const RxLeft& left, const uint8_t* d_block, uint32_t n_socks,
+                          const RxLaunch& how) {
+    uint8_t* const scratch = left.deliver_scratch;
+    const DeliverScratch& s = left.ds;
+    const uint32_t n = b.n;
+    const hipStream_t stream = how.stream;
     DlArgs a;
-    a.frames = frames;
-    a.offsets = offsets;
-    a.sorted = reinterpret_cast<const uint64_t*>(flow_scratch + fs.sorted);
-    a.rec = reinterpret_cast<const uint2*>(flow_scratch + fs.rec);
-    a.keys = reinterpret_cast<const uint4*>(flow_scratch + fs.keys);
-    a.flowidx = reinterpret_cast<const uint32_t*>(flow_scratch + fs.flowidx);
-    a.totals = totals;
+    static_cast<FlowView&>(a) = flow_view(left, n);
+    a.frames = b.frames;
+    a.offsets = b.offsets;
+    a.totals = static_cast<const fs_rx_flow_totals*>(r.totals());
     a.socks = reinterpret_cast<const fs_rx_sock*>(d_block);
     a.table = reinterpret_cast<const uint32_t*>(d_block + dl::block_of(n_socks).table);
     a.flow_sock = reinterpret_cast<uint32_t*>(scratch + s.flow_sock);
     a.mk = reinterpret_cast<uint2*>(scratch + s.mk);
     a.dwpos = reinterpret_cast<uint32_t*>(scratch + s.dwpos);
     a.sock_first = reinterpret_cast<uint32_t*>(scratch + s.sock_first);
-    a.rings = rings;
-    a.socks_out = socks_out;
-    a.delivered = delivered;
+    a.rings = r.rings;
+    a.socks_out = r.socks_out();
+    a.delivered = r.delivered();
     a.n = n;
     a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
     a.n_socks = n_socks;
     a.tmask = flows::table_slots(n_socks) - 1u;
-    a.hash_mask = hash_mask;
-    a.b = flows::index_bits(n);
-    const uint32_t cap = (uint32_t)(max_workgroups > 0 ? max_workgroups : 1);
+    a.hash_mask = how.hash_mask;
+    const uint32_t cap = (uint32_t)(how.max_workgroups > 0 ? how.max_workgroups : 1);
     const uint32_t n_tiles = (uint32_t)(((uint64_t)n + kTileFrames - 1) / kTileFrames);
     const uint32_t walk_blocks = (n_socks + kWaves - 1u) / kWaves;
     hipError_t e = hipMemsetAsync(scratch + s.dwpos, 0xFF, 4ull * n + 4ull * n_socks, stream);

@@ -294,14 +294,13 @@ FlowScratch flows_scratch(uint32_t n) {
     return s;
 }
 
-hipError_t launch_coalesce_flows(const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
-                                 uint32_t flags, const uint8_t* status, uint8_t* payload, uint64_t payload_cap,
-                                 fs_rx_run* runs, fs_rx_flow* flows_out, uint32_t* order, uint32_t* run_of,
-                                 fs_rx_flow_totals* totals, uint8_t* scratch, const FlowScratch& s, uint32_t hash_mask,
-                                 int max_workgroups, uint32_t steps, hipStream_t stream) {
+hipError_t launch_coalesce_flows(const RxBatch& b, const RxResults& r, const RxLeft& left, const RxLaunch& how) {
+    uint8_t* const scratch = left.flow_scratch;
+    const FlowScratch& s = left.fs;
+    const uint32_t n = b.n, steps = how.steps;
+    const hipStream_t stream = how.stream;
     FlArgs a;
-    const GatherGrids g = fill_gather_args(a, frames, offsets, lengths, n, flags, status, payload, payload_cap, runs, run_of,
-                                           scratch, s, max_workgroups);
+    const GatherGrids g = fill_gather_args(a, b, r, scratch, s, how.max_workgroups);
     a.keys = reinterpret_cast<uint4*>(scratch + s.keys);
     a.table = reinterpret_cast<uint32_t*>(scratch + s.table);
     a.rep = reinterpret_cast<uint32_t*>(scratch + s.rep);
@@ -310,11 +309,11 @@ hipError_t launch_coalesce_flows(const uint8_t* frames, const uint64_t* offsets,
     a.sorted = reinterpret_cast<uint64_t*>(scratch + s.sorted);
     a.flowidx = reinterpret_cast<uint32_t*>(scratch + s.flowidx);
     a.fhidx = reinterpret_cast<uint32_t*>(scratch + s.fhidx);
-    a.flows = flows_out;
-    a.order = order;
-    a.totals = totals;
+    a.flows = r.flows();
+    a.order = r.order();
+    a.totals = static_cast<fs_rx_flow_totals*>(r.totals());
     a.tmask = flows::table_slots(n) - 1u;
-    a.hash_mask = hash_mask;
+    a.hash_mask = how.hash_mask;
     a.b = flows::index_bits(n);
     hipError_t e = hipSuccess;
     if (steps & kFlowStepOrder) {

@@ -10,6 +10,7 @@
 #include "../../include/framesum_deliver.h"
 #include "../../include/framesum_recv.h"
 #include "framesum_choice.h"
+#include "framesum_plan.h"
 
 namespace framesum {
 
@@ -97,68 +98,105 @@ hipError_t launch_send_rings(const uint8_t* d_block, const segment::Block& b, ui
                              uint8_t* status, uint32_t mtu, uint32_t flags, uint32_t align, const SegTables* tables,
                              int workgroups, hipStream_t stream);
 
-// ---- RX coalesce (framesum_coalesce.hip). The launches that follow a batch's digest launch on
-// `stream`: classify, the scan's three steps and the copy (fs_coalesce_batch in include/framesum.h).
-// `status`: the batch's verdicts, as that digest launch writes them. `scratch`: coalesce_scratch(n).bytes
-// of device memory, 8-byte aligned, whose sub-arrays lie at the offsets CoScratch names; `copied` is
-// the 64-bit count of leading payload bytes the copy writes (the whole of it unless payload_cap cuts
-// it short). `max_workgroups` caps every grid.
+// ---- The RX calls (framesum_coalesce.hip, framesum_flows.hip, framesum_deliver.hip, framesum_recv.hip).
+// A call is a row of stages on one stream -- the digest launch and the plain or the flow-aware gather,
+// then the delivery, then the receive call's fold -- each behind the one before it and reading what it
+// left. The launches take the call as a few records.
+
+// The batch as the launches read it.
+struct RxBatch {
+    const uint8_t* frames;
+    const uint64_t* offsets;
+    const uint32_t* lengths;
+    uint32_t n, mtu, flags;
+};
+// Where the results go on the device: the caller's pointers in the device forms, the context's device
+// arrays in the host forms. `array` holds the arrays framesum_plan.h describes (plan::rx::Array), null
+// where the call has none or the caller passed none (the kernels skip those stores); the accessors
+// give them their types. `totals` is an fs_rx_totals in the plain call, an fs_rx_flow_totals in the others.
+struct RxResults {
+    uint8_t* payload;
+    uint64_t payload_cap;
+    fs_digest* out;
+    uint8_t* status;
+    uint8_t* rings;
+    void* array[plan::rx::kArrays];
+    template <class T>
+    T* as(plan::rx::Array a) const { return static_cast<T*>(array[a]); }
+    void* totals() const { return array[plan::rx::kTotals]; }
+    fs_rx_run* runs() const { return as<fs_rx_run>(plan::rx::kRuns); }
+    fs_rx_flow* flows() const { return as<fs_rx_flow>(plan::rx::kFlowRecs); }
+    uint32_t* order() const { return as<uint32_t>(plan::rx::kOrder); }
+    uint32_t* run_of() const { return as<uint32_t>(plan::rx::kRunOf); }
+    uint8_t* delivered() const { return as<uint8_t>(plan::rx::kDelivered); }
+    fs_rx_sock_out* socks_out() const { return as<fs_rx_sock_out>(plan::rx::kSocksOut); }
+    fs_rx_snd_out* snd_out() const { return as<fs_rx_snd_out>(plan::rx::kSndOut); }
+    uint8_t* code() const { return as<uint8_t>(plan::rx::kCode); }
+};
+// How a call's own launches (not the digest's) go: `max_workgroups` caps every grid; `hash_mask` is ANDed
+// with a key's hash (all ones in the product); `steps`: which of the flow launches' three groups to
+// enqueue, all of them in every call of the ABI (the test library times the sort alone on the keys an
+// earlier call has left).
+constexpr uint32_t kFlowStepOrder = 1, kFlowStepSort = 2, kFlowStepGather = 4, kFlowStepsAll = 7;
+struct RxLaunch {
+    int max_workgroups;
+    uint32_t hash_mask, steps;
+    hipStream_t stream;
+};
+
+// The scratch layouts. CoScratch: the plain gather's, 8-byte aligned; `copied` is the 64-bit count of
+// leading payload bytes the copy writes (the whole of it unless payload_cap cuts it short).
+// FlowScratch: the flow launches', 256-byte aligned (flows_scratch asks the sort for its temporary
+// storage's size, so callers compute it once per call). DeliverScratch and RecvScratch: 8-byte aligned.
 struct CoScratch {
     uint64_t rec, payoff, partial, prefix, copied, runidx, hidx, bytes;
 };
-CoScratch coalesce_scratch(uint32_t n);
-hipError_t launch_coalesce(const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
-                           uint32_t flags, const uint8_t* status, uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs,
-                           uint32_t* run_of, fs_rx_totals* totals, uint8_t* scratch, int max_workgroups,
-                           hipStream_t stream);
-
-// ---- Flow-aware RX coalesce (framesum_flows.hip). The launches that follow a batch's digest launch
-// on `stream` (fs_coalesce_flows_batch in include/framesum.h): the delivery order (keys, flow table,
-// sort keys), the sort, and the scans and the copy over delivery slots. `scratch`: `s.bytes` of device
-// memory, 256-byte aligned, `s` = flows_scratch(n) (which asks the sort for its temporary storage's
-// size, so callers compute it once per call). `hash_mask` is ANDed with a key's hash (all ones in
-// the product). `steps`: which of the three groups to enqueue, all of them in every call of the ABI;
-// the test library times the sort alone on the keys an earlier call has left.
 struct FlowScratch {
     uint64_t keys, sk_in, sorted, rec, payoff, partial, prefix, copied, table, rep, slot_of, runidx, hidx, flowidx, fhidx,
         sort_temp, sort_bytes, bytes;
 };
-constexpr uint32_t kFlowStepOrder = 1, kFlowStepSort = 2, kFlowStepGather = 4, kFlowStepsAll = 7;
-FlowScratch flows_scratch(uint32_t n);
-hipError_t launch_coalesce_flows(const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths, uint32_t n,
-                                 uint32_t flags, const uint8_t* status, uint8_t* payload, uint64_t payload_cap,
-                                 fs_rx_run* runs, fs_rx_flow* flows_out, uint32_t* order, uint32_t* run_of,
-                                 fs_rx_flow_totals* totals, uint8_t* scratch, const FlowScratch& s, uint32_t hash_mask,
-                                 int max_workgroups, uint32_t steps, hipStream_t stream);
-
-// ---- In-order TCP delivery (framesum_deliver.hip). The launches that follow a batch's flow launches
-// on `stream` (fs_deliver_flows_batch in include/framesum_deliver.h) and read what those left in
-// `flow_scratch` (laid out as `fs`) and in `totals`. `d_block`: the device copy of the staged block
-// (framesum_deliver.h block_of: the socket records, then the socket table). `scratch`:
-// deliver_scratch(n, n_socks).bytes of device memory, 8-byte aligned. With n of 0 only the sockets'
-// out records are written. `max_workgroups` caps every grid.
 struct DeliverScratch {
     uint64_t mk, dwpos, sock_first, flow_sock, bytes;
 };
-DeliverScratch deliver_scratch(uint32_t n, uint32_t n_socks);
-hipError_t launch_deliver(const uint8_t* frames, const uint64_t* offsets, uint32_t n, const uint8_t* flow_scratch,
-                          const FlowScratch& fs, const fs_rx_flow_totals* totals, const uint8_t* d_block, uint32_t n_socks,
-                          uint32_t hash_mask, uint8_t* rings, fs_rx_sock_out* socks_out, uint8_t* delivered,
-                          uint8_t* scratch, const DeliverScratch& s, int max_workgroups, hipStream_t stream);
-
-// ---- The send side of the receive call (framesum_recv.hip). The launches that follow a batch's
-// delivery launches on `stream` (fs_recv_flows_batch in include/framesum_recv.h) and read what those
-// left in `flow_scratch` (laid out as `fs`), in `deliver_scratch` (laid out as `ds`) and in `socks_out`.
-// `d_block`: the device copy of the staged block (framesum_recv.h stage: one Sock per socket).
-// `scratch`: recv_scratch(n).bytes of device memory, 8-byte aligned. `code` is nullable, and zeroed by
-// the caller. With n of 0 only the sockets' out records are written. `max_workgroups` caps every grid.
 struct RecvScratch {
     uint64_t aw, bytes;
 };
+CoScratch coalesce_scratch(uint32_t n);
+FlowScratch flows_scratch(uint32_t n);
+DeliverScratch deliver_scratch(uint32_t n, uint32_t n_socks);
 RecvScratch recv_scratch(uint32_t n);
-hipError_t launch_recv(const uint8_t* frames, const uint64_t* offsets, uint32_t n, const uint8_t* flow_scratch,
-                       const FlowScratch& fs, const uint8_t* deliver_scratch, const DeliverScratch& ds,
-                       const fs_rx_sock_out* socks_out, const uint8_t* d_block, uint32_t n_socks, fs_rx_snd_out* snd_out,
-                       uint8_t* code, uint8_t* scratch, const RecvScratch& s, int max_workgroups, hipStream_t stream);
+
+// What the stages of one call leave on the device for the stages behind them: each stage's scratch, laid
+// out as its layout says (all zero for a stage that has not run: an empty batch has no flow stage), and
+// where the gather's count of written payload bytes lies.
+struct RxLeft {
+    const uint8_t* copied;
+    uint8_t* flow_scratch;
+    FlowScratch fs;
+    uint8_t* deliver_scratch;
+    DeliverScratch ds;
+    uint8_t* recv_scratch;
+    RecvScratch rs;
+};
+
+// The launches that follow a batch's digest launch on the stream (fs_coalesce_batch in
+// include/framesum.h): classify, the scan's three steps and the copy. `r.status`: the batch's verdicts,
+// as that digest launch writes them. `scratch`: coalesce_scratch(n).bytes of device memory.
+hipError_t launch_coalesce(const RxBatch& b, const RxResults& r, uint8_t* scratch, const RxLaunch& how);
+// ... (fs_coalesce_flows_batch): the delivery order (keys, flow table, sort keys), the sort, and the
+// scans and the copy over delivery slots, in `left.flow_scratch` laid out as `left.fs`.
+hipError_t launch_coalesce_flows(const RxBatch& b, const RxResults& r, const RxLeft& left, const RxLaunch& how);
+// The launches that follow a batch's flow launches (fs_deliver_flows_batch in
+// include/framesum_deliver.h) and read what those left. `d_block`: the device copy of the staged block
+// (framesum_deliver.h block_of: the socket records, then the socket table). With n of 0 only the
+// sockets' out records are written.
+hipError_t launch_deliver(const RxBatch& b, const RxResults& r, const RxLeft& left, const uint8_t* d_block, uint32_t n_socks,
+                          const RxLaunch& how);
+// The launches that follow a batch's delivery launches (fs_recv_flows_batch in include/framesum_recv.h)
+// and read what the flow and the delivery launches left, and `r.socks_out()`. `d_block`: the device copy
+// of the staged block (framesum_recv.h stage: one Sock per socket). `r.code()` is zeroed by the caller.
+// With n of 0 only the sockets' out records are written.
+hipError_t launch_recv(const RxBatch& b, const RxResults& r, const RxLeft& left, const uint8_t* d_block, uint32_t n_socks,
+                       const RxLaunch& how);
 
 }  // namespace framesum

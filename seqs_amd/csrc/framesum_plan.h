@@ -1,7 +1,7 @@
 // Host-side planning for the framesum entry points, free of HIP so that it compiles on its
 // own: the chunks of a host-staged batch (fs_digest_batch_host), the byte-balanced blocks of
-// fs_digest_batch_multi, and the round-robin shard maps of fs_digest_batch_sharded and its
-// de-interleave kernel. The library includes it; tests/csrc/test_plan.cpp builds it alone
+// fs_digest_batch_multi, the round-robin shard maps of fs_digest_batch_sharded and its
+// de-interleave kernel, and the device result arrays of the RX host forms. The library includes it; tests/csrc/test_plan.cpp builds it alone
 // under ASan + UBSan (sanitizers on the host code) and checks every invariant
 // on random, out-of-order, overlapping and edge-case batches.
 #pragma once
@@ -215,6 +215,82 @@ inline void host_chunks(const uint64_t* offsets, const uint32_t* lengths, uint32
         c0 = c1;
     }
 }
+
+// ---------------------------------------------------------------------------------------
+// The device result arrays of the four RX host forms (fs_coalesce_batch_host,
+// fs_coalesce_flows_batch_host, fs_deliver_flows_batch_host, fs_recv_flows_batch_host), described
+// once: which arrays a call kind has, what each is sized by, where each lies in the context's one
+// buffer, and how much of each comes back given the totals the device reported. The host forms carve
+// the buffer and copy back by walking this description (framesum_api_rx.cpp).
+namespace rx {
+
+// A kind has the arrays of the kinds before it and its own.
+enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv };
+enum Array : uint32_t { kTotals, kRuns, kFlowRecs, kOrder, kRunOf, kDelivered, kSocksOut, kSndOut, kCode, kArrays };
+// What counts an array's entries: one record, the batch's frames, the call's sockets, or (for what
+// comes back only) one of the totals.
+enum Count : uint32_t { kOne, kPerFrame, kPerSock, kNRuns, kNFlows, kNAccepted };
+struct Totals {
+    uint64_t n_runs, n_flows, n_accepted;  // (the plain call reports runs only)
+};
+struct ArrayDesc {
+    Kind from;             // the first kind that has the array
+    uint32_t elem, align;  // bytes per entry (kTotals: see totals_bytes), and the alignment its type needs
+    Count room, back;      // entries it has room for, entries that come back
+};
+constexpr ArrayDesc kArrayDesc[kArrays] = {
+    {kPlain, 0, 8, kOne, kOne},               // fs_rx_totals / fs_rx_flow_totals
+    {kPlain, 24, 8, kPerFrame, kNRuns},       // fs_rx_run
+    {kFlows, 32, 8, kPerFrame, kNFlows},      // fs_rx_flow
+    {kFlows, 4, 4, kPerFrame, kNAccepted},    // order
+    {kPlain, 4, 4, kPerFrame, kPerFrame},     // run_of
+    {kDeliver, 1, 1, kPerFrame, kPerFrame},   // delivered
+    {kDeliver, 32, 8, kPerSock, kPerSock},    // fs_rx_sock_out
+    {kRecv, 32, 8, kPerSock, kPerSock},       // fs_rx_snd_out
+    {kRecv, 1, 1, kPerFrame, kPerFrame},      // code
+};
+constexpr uint64_t totals_bytes(Kind kind) { return kind == kPlain ? 16 : 24; }
+constexpr uint64_t elem_bytes(Kind kind, Array a) { return a == kTotals ? totals_bytes(kind) : kArrayDesc[a].elem; }
+constexpr uint64_t count_of(Count c, uint64_t n, uint64_t n_socks, const Totals& t) {
+    return c == kOne ? 1 : c == kPerFrame ? n : c == kPerSock ? n_socks : c == kNRuns ? t.n_runs : c == kNFlows ? t.n_flows : t.n_accepted;
+}
+
+// Whether the totals the device reported can be a batch of n frames' (every count that sizes a copy
+// back is then within its array's room).
+constexpr bool consistent(Kind kind, uint64_t n, const Totals& t) {
+    return kind == kPlain ? t.n_runs <= n : t.n_accepted <= n && t.n_runs <= t.n_accepted && t.n_flows <= t.n_runs;
+}
+
+// Where the arrays of a call of `kind` over n frames and n_socks sockets lie: byte offsets from an
+// 8-byte aligned base (kAbsent: the kind has no such array), each aligned for its type, in the order of
+// Array; `room` bytes each, `bytes` in all.
+constexpr uint64_t kAbsent = ~uint64_t(0);
+struct Layout {
+    uint64_t at[kArrays], room[kArrays], bytes;
+    bool has(Array a) const { return at[a] != kAbsent; }
+};
+inline Layout layout(Kind kind, uint64_t n, uint64_t n_socks) {
+    Layout L;
+    uint64_t at = 0;
+    for (uint32_t a = 0; a < kArrays; ++a) {
+        const ArrayDesc& d = kArrayDesc[a];
+        L.at[a] = kAbsent;
+        L.room[a] = 0;
+        if (kind < d.from) continue;
+        at = (at + d.align - 1) / d.align * d.align;
+        L.at[a] = at;
+        L.room[a] = elem_bytes(kind, (Array)a) * count_of(d.room, n, n_socks, Totals{0, 0, 0});
+        at += L.room[a];
+    }
+    L.bytes = at;
+    return L;
+}
+// The bytes of array `a` that come back to the caller, given consistent totals `t`.
+constexpr uint64_t bytes_back(Kind kind, Array a, uint64_t n, uint64_t n_socks, const Totals& t) {
+    return kind < kArrayDesc[a].from ? 0 : elem_bytes(kind, a) * count_of(kArrayDesc[a].back, n, n_socks, t);
+}
+
+}  // namespace rx
 
 // ---------------------------------------------------------------------------------------
 // fs_digest_batch_multi blocks: nctx blocks of about equal byte counts. The blocks are

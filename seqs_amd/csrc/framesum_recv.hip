@@ -36,13 +36,9 @@ namespace {
 using namespace codev;
 namespace rv = recv;
 
-struct RvArgs {
+struct RvArgs : FlowView {  // (the flow launches' scratch of this call)
     const uint8_t* frames;
     const uint64_t* offsets;
-    // the flow launches' scratch of this call
-    const uint64_t* sorted;   // per slot: the sort key, whose low b bits are the frame
-    const uint2* rec;         // per slot
-    const uint32_t* flowidx;  // per slot
     // the delivery launches' scratch and result of this call
     const uint32_t* flow_sock;
     const uint2* mk;
@@ -55,10 +51,8 @@ struct RvArgs {
     uint2* aw;  // per slot of a matched flow: Ack, the dword at L4 + 12
     fs_rx_snd_out* snd_out;
     uint8_t* code;
-    uint32_t n, n_blocks, n_socks, b;
+    uint32_t n, n_blocks, n_socks;
 };
-
-__device__ __forceinline__ uint32_t slot_frame(const RvArgs& a, uint32_t k) { return flows::sort_index(a.sorted[k], a.b); }
 
 __global__ void __launch_bounds__(kThreads) recv_gather(const RvArgs a) {
     for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
@@ -97,10 +91,6 @@ struct ScanStorage {
     KeyScan::storage_type key;
 };
 __device__ __forceinline__ unsigned long long lanes_upto(uint32_t l) { return l >= 63u ? ~0ull : (2ull << l) - 1ull; }
-// Lane `l`'s value, l the same in all lanes.
-__device__ __forceinline__ uint32_t lane_value(uint32_t v, uint32_t l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane((int)l));
-}
 
 // The walk's state between chunks, the same in all lanes.
 struct Walk {
@@ -208,30 +198,29 @@ RecvScratch recv_scratch(uint32_t n) {
     return s;
 }
 
-hipError_t launch_recv(const uint8_t* frames, const uint64_t* offsets, uint32_t n, const uint8_t* flow_scratch,
-                       const FlowScratch& fs, const uint8_t* deliver_scratch, const DeliverScratch& ds,
-                       const fs_rx_sock_out* socks_out, const uint8_t* d_block, uint32_t n_socks, fs_rx_snd_out* snd_out,
-                       uint8_t* code, uint8_t* scratch, const RecvScratch& s, int max_workgroups, hipStream_t stream) {
+hipError_t launch_recv(const RxBatch& b, const RxResults& r, const RxLeft& left, const uint8_t* d_block, uint32_t n_socks,
+                       const RxLaunch& how) {
+    const uint8_t* const deliver_scratch = left.deliver_scratch;
+    const DeliverScratch& ds = left.ds;
+    const uint32_t n = b.n;
+    const hipStream_t stream = how.stream;
     RvArgs a;
-    a.frames = frames;
-    a.offsets = offsets;
-    a.sorted = reinterpret_cast<const uint64_t*>(flow_scratch + fs.sorted);
-    a.rec = reinterpret_cast<const uint2*>(flow_scratch + fs.rec);
-    a.flowidx = reinterpret_cast<const uint32_t*>(flow_scratch + fs.flowidx);
+    static_cast<FlowView&>(a) = flow_view(left, n);
+    a.frames = b.frames;
+    a.offsets = b.offsets;
     a.flow_sock = reinterpret_cast<const uint32_t*>(deliver_scratch + ds.flow_sock);
     a.mk = reinterpret_cast<const uint2*>(deliver_scratch + ds.mk);
     a.dwpos = reinterpret_cast<const uint32_t*>(deliver_scratch + ds.dwpos);
     a.sock_first = reinterpret_cast<const uint32_t*>(deliver_scratch + ds.sock_first);
-    a.socks_out = socks_out;
+    a.socks_out = r.socks_out();
     a.socks = reinterpret_cast<const rv::Sock*>(d_block);
-    a.aw = reinterpret_cast<uint2*>(scratch + s.aw);
-    a.snd_out = snd_out;
-    a.code = code;
+    a.aw = reinterpret_cast<uint2*>(left.recv_scratch + left.rs.aw);
+    a.snd_out = r.snd_out();
+    a.code = r.code();
     a.n = n;
     a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
     a.n_socks = n_socks;
-    a.b = flows::index_bits(n);
-    const uint32_t cap = (uint32_t)(max_workgroups > 0 ? max_workgroups : 1);
+    const uint32_t cap = (uint32_t)(how.max_workgroups > 0 ? how.max_workgroups : 1);
     const uint32_t walk_blocks = (n_socks + kWaves - 1u) / kWaves;
     if (n != 0) hipLaunchKernelGGL(recv_gather, dim3(a.n_blocks < cap ? a.n_blocks : cap), dim3(kThreads), 0, stream, a);
     hipLaunchKernelGGL(recv_walk, dim3(walk_blocks < cap ? walk_blocks : cap), dim3(kThreads), 0, stream, a);

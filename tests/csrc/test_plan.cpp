@@ -2,7 +2,8 @@
 // (tests/csrc/Makefile, run by tests/test_host_sanitizers.py): the chunks of the
 // host-staged path, the blocks of fs_digest_batch_multi and the round-robin shard / gather /
 // de-interleave maps, on random batches that are in order, shuffled, sparse, overlapping,
-// empty, zero-length, huge-offset, and with more contexts than frames.
+// empty, zero-length, huge-offset, and with more contexts than frames; and the description of the
+// RX host forms' device result arrays, for every call kind up to 2^30 frames.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -406,8 +407,85 @@ static void replay_chunks(uint64_t n, uint32_t N, uint32_t maxc, uint64_t target
     for (uint64_t g = 0; g < n; ++g) CHECK(wrote[g] == 1);
 }
 
+// The device result arrays of the four RX host forms (plan::rx): for every call kind, batch size and
+// socket count, the arrays the kind has (stated here again, not read from the header's table), their
+// alignment, that they are disjoint and inside the total, that nothing wraps (the sums again in 128
+// bits), the predicate on the totals, and that no accepted totals bring back more than an array holds.
+static void check_rx_arrays(uint32_t kind_index, uint64_t n, uint64_t n_socks) {
+    namespace rx = framesum::plan::rx;
+    typedef unsigned __int128 u128;
+    const rx::Kind kind = (rx::Kind)kind_index;
+    struct Want {
+        rx::Array a;
+        uint32_t from;  // the first kind that has it: 0 plain, 1 flows, 2 delivery, 3 receive
+        uint64_t elem, align;
+        bool per_sock;
+    };
+    const Want want[] = {{rx::kTotals, 0, kind_index == 0 ? 16u : 24u, 8, false},
+                         {rx::kRuns, 0, 24, 8, false},     {rx::kFlowRecs, 1, 32, 8, false}, {rx::kOrder, 1, 4, 4, false},
+                         {rx::kRunOf, 0, 4, 4, false},     {rx::kDelivered, 2, 1, 1, false}, {rx::kSocksOut, 2, 32, 8, true},
+                         {rx::kSndOut, 3, 32, 8, true},    {rx::kCode, 3, 1, 1, false}};
+    CHECK(sizeof want / sizeof want[0] == rx::kArrays);  // every array is one of these, and no other
+    const rx::Layout L = rx::layout(kind, n, n_socks);
+    u128 sum = 0, pad = 0;
+    uint32_t seen = 0;
+    for (const Want& w : want) {
+        const bool present = kind_index >= w.from;
+        seen |= 1u << w.a;
+        CHECK(L.has(w.a) == present);
+        if (!present) {
+            CHECK(L.room[w.a] == 0);
+            CHECK(rx::bytes_back(kind, w.a, n, n_socks, rx::Totals{n, n, n}) == 0);
+            continue;
+        }
+        const u128 room = (u128)w.elem * (w.a == rx::kTotals ? 1 : w.per_sock ? n_socks : n);
+        CHECK((u128)L.room[w.a] == room);
+        CHECK(L.at[w.a] % w.align == 0);
+        CHECK((u128)L.at[w.a] + room <= (u128)L.bytes);
+        sum += room;
+        pad += w.align - 1;
+        for (const Want& v : want)  // pairwise disjoint
+            if (v.a < w.a && kind_index >= v.from)
+                CHECK((u128)L.at[v.a] + L.room[v.a] <= (u128)L.at[w.a] || (u128)L.at[w.a] + room <= (u128)L.at[v.a]);
+    }
+    CHECK(seen == (1u << rx::kArrays) - 1u);
+    CHECK((u128)L.bytes >= sum && (u128)L.bytes <= sum + pad);
+    // the totals a device may report: around 0, the middle and n in every field
+    const uint64_t around[] = {0, 1, n / 2, n ? n - 1 : 0, n, n + 1};
+    for (uint64_t runs : around)
+        for (uint64_t flows : around)
+            for (uint64_t acc : around) {
+                const rx::Totals t{runs, flows, acc};
+                const bool ok = kind_index == 0 ? runs <= n : acc <= n && runs <= acc && flows <= runs;
+                CHECK(rx::consistent(kind, n, t) == ok);
+                if (!ok) continue;
+                for (const Want& w : want) {
+                    if (kind_index < w.from) continue;
+                    const uint64_t count = w.a == rx::kTotals ? 1 : w.a == rx::kRuns ? runs : w.a == rx::kFlowRecs ? flows
+                                           : w.a == rx::kOrder ? acc : w.per_sock ? n_socks : n;
+                    const uint64_t back = rx::bytes_back(kind, w.a, n, n_socks, t);
+                    CHECK((u128)back == (u128)w.elem * count);
+                    CHECK(back <= L.room[w.a]);
+                }
+            }
+    // each way of being inconsistent, by name
+    CHECK(!rx::consistent(rx::kPlain, n, rx::Totals{n + 1, 0, 0}));
+    if (kind_index != 0) {
+        CHECK(!rx::consistent(kind, n, rx::Totals{n + 1, 0, n}));          // n_runs > n
+        CHECK(!rx::consistent(kind, n, rx::Totals{0, 0, n + 1}));          // n_accepted > n
+        CHECK(!rx::consistent(kind, n, rx::Totals{n / 2 + 1, 0, n / 2}));  // n_runs > n_accepted
+        CHECK(!rx::consistent(kind, n, rx::Totals{n / 2, n / 2 + 1, n}));  // n_flows > n_runs
+        CHECK(rx::consistent(kind, n, rx::Totals{n / 2, n / 2, n}));
+    }
+}
+
 int main() {
     std::mt19937_64 rng(12345);
+    for (uint32_t kind = 0; kind < 4; ++kind)
+        for (uint64_t n : {uint64_t(0), uint64_t(1), uint64_t(2), uint64_t(3), uint64_t(63), uint64_t(64), uint64_t(65),
+                           uint64_t(255), uint64_t(256), uint64_t(257), uint64_t(65793), uint64_t(1) << 30})
+            for (uint64_t n_socks : {uint64_t(0), uint64_t(1), uint64_t(3), uint64_t(64), uint64_t(65536)})
+                check_rx_arrays(kind, n, n_socks);
     // chunks: every batch kind, several chunk sizes (small ones force many chunks)
     for (int kind = 0; kind < 5; ++kind)
         for (uint32_t n : {0u, 1u, 2u, 7u, 63u, 64u, 65u, 1000u, 5000u})

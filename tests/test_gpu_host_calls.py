@@ -2,9 +2,12 @@
 fs_segment_batch_host, fs_coalesce_batch_host, fs_coalesce_flows_batch_host), taken together: the
 buffers grow, are reused at a stale larger capacity and pass from one call to the next; the calls
 recover after a host-staged digest that failed half-way; and each rejects a frame that ends past
-frames_bytes. Expected results come from the restatements the calls' own suites use
-(tests/coalesce_ref.py, tests/flows_ref.py, tests/segment_ref.py, the C oracle's fill_batch), and
-every comparison is the WHOLE buffer byte for byte, noise tails included."""
+frames_bytes. Then the eight RX entry points (the plain and the flow-aware coalesce, the delivery and
+the receive call, device and host forms) through their raw prototypes, with each nullable array left
+out in turn. Expected results come from the restatements the calls' own suites use
+(tests/coalesce_ref.py, tests/flows_ref.py, tests/deliver_ref.py, tests/recv_ref.py,
+tests/segment_ref.py, the C oracle's fill_batch), and every comparison is the WHOLE buffer byte for
+byte, noise tails included."""
 import numpy as np
 import pytest
 
@@ -244,3 +247,130 @@ def test_frames_past_frames_bytes_are_rejected(eng):
         assert np.array_equal(work[: buf.size], before)  # a rejected call writes nothing
     # ... and the context still works
     do_fill(eng, 16, 52, FILL_CSUM | FCS_APPEND)
+
+
+# ---- 4. the eight RX entry points with each nullable array left out -------------------------------
+
+RX_BASES = ("fs_coalesce_batch", "fs_coalesce_flows_batch", "fs_deliver_flows_batch", "fs_recv_flows_batch")
+# (argument, the first of RX_BASES that has it): what the headers let a caller pass as NULL
+RX_NULLABLE = (("run_of", 0), ("out", 0), ("status", 0), ("payload", 0), ("flows", 1), ("delivered", 2), ("code", 3))
+PLEAD = 3  # the payload starts at an odd address
+
+
+def rx_pin_case():
+    """19 frames: three interleaved TCP flows of six segments, a UDP frame among them and one segment
+    with a damaged checksum; three sockets, two with a flow of the batch and one without. n and
+    n_socks are odd, so that an array lying where another should is misaligned or cut short. The
+    expected results of the four call kinds come from their suites' restatements."""
+    import deliver_ref as dref
+    import recv_ref as rref
+    from test_gpu_deliver import sock_for
+
+    rng = np.random.default_rng(71)
+    hdrs = [fref.flow_header(rng, 0x1000 + f) for f in range(3)]
+    segs = [fref.segments(rng, h, 1000 * (f + 1), [100, 37, 64, 1, 90, 55]) for f, h in enumerate(hdrs)]
+    frames = [segs[g][k] for g, k in fref.interleave([range(6)] * 3)]
+    frames.insert(4, fref.udp_frame(rng, b"a udp datagram"))
+    frames = fref.finish(frames)
+    bad = bytearray(frames[9])  # flow 2's third segment
+    bad[60] ^= 0x10
+    frames[9] = bytes(bad)
+    socks = dref.socks_of(sock_for(hdrs[2], 3000, 7, 600), sock_for(fref.flow_header(rng, 0x7777), 5, 620, 64, ring_wpos=9, ring_free=30),
+                          sock_for(hdrs[0], 1000, 700, 500, ring_wpos=450))
+    snd = rref.snd_of(*[((int(s["snd_nxt"]) - 100) % (1 << 32), 1000) for s in socks])
+    buf, off, ln = fref.pack(frames, lead=3)
+    room = int(ln.sum())
+    noise = np.random.default_rng(72).integers(0, 256, PLEAD + room + TAIL, dtype=np.uint8)
+    rings = np.random.default_rng(73).integers(0, 256, 1300, dtype=np.uint8)
+    assert ln.size == 19 and socks.size == 3
+    e = [cref.expected(buf, off, ln, 0, 0, noise, PLEAD, room), fref.expected(buf, off, ln, 0, 0, noise, PLEAD, room),
+         dref.expected(buf, off, ln, 0, 0, noise, PLEAD, room, socks, rings),
+         rref.expected(buf, off, ln, 0, 0, noise, PLEAD, room, socks, snd, rings)]
+    assert e[3]["n_flows"] == 4 and e[3]["n_accepted"] == 18 and e[3]["st"][9] != 0
+    assert [int(x) for x in e[3]["socks_out"]["n_delivered"]] == [2, 0, 6] and (e[3]["delivered"] == 2).sum() == 3
+    assert int(e[3]["socks_out"]["ring_wpos"][2]) < 450 and e[3]["code"].any()  # the third socket's ring wraps
+    return dict(buf=buf, off=off, ln=ln, n=19, socks=socks, snd=snd, room=room, noise=noise, rings=rings, expected=e)
+
+
+def rx_pin_call(eng, kind, host, case, omit=()):
+    """One call of RX_BASES[kind] (`host`: its host form) through the raw prototype, every result array
+    filled with a pattern first. `omit`: the nullable arguments that go as NULL (`payload` with a cap
+    of 0). Returns the bytes of every array that was passed, of `rings` and of the totals."""
+    import torch
+
+    n, n_socks = case["n"], int(case["socks"].size)
+    sizes = dict(runs=24 * n, run_of=4 * n, totals=16 if kind == 0 else 24, out=8 * n, status=n)
+    if kind >= 1:
+        sizes.update(flows=32 * n, order=4 * n)
+    if kind >= 2:
+        sizes.update(socks_out=32 * n_socks, delivered=n)
+    if kind == 3:
+        sizes.update(snd_out=32 * n_socks, code=n)
+    results = {k: np.full(v, 0xA5, dtype=np.uint8) for k, v in sizes.items()}
+    results["payload"] = case["noise"].copy()
+    if kind >= 2:
+        results["rings"] = case["rings"].copy()
+    held = dict(results, frames=case["buf"], offsets=case["off"].view(np.uint8), lengths=case["ln"].view(np.uint8))
+    if host:
+        at = lambda k: held[k].ctypes.data  # noqa: E731
+    else:
+        held = {k: torch.from_numpy(v).to("cuda:0") for k, v in held.items()}
+        at = lambda k: held[k].data_ptr()  # noqa: E731
+    nullable = lambda k: None if k in omit else at(k)  # noqa: E731
+    args = [eng._ctx, at("frames")] + ([case["buf"].size] if host else []) + [at("offsets"), at("lengths"), n, 0, 0]
+    if kind >= 2:
+        args += [case["socks"].ctypes.data, n_socks, at("rings"), case["rings"].size, at("socks_out"), nullable("delivered")]
+    if kind == 3:
+        args += [case["snd"].ctypes.data, at("snd_out"), nullable("code")]
+    args += [None, 0] if "payload" in omit else [at("payload") + PLEAD, case["room"]]
+    args += [at("runs")] + ([nullable("flows"), at("order")] if kind >= 1 else [])
+    args += [nullable("run_of"), at("totals"), nullable("out"), nullable("status")]
+    if not host:
+        args.append(torch.cuda.current_stream().cuda_stream)
+    name = RX_BASES[kind] + ("_host" if host else "")
+    st = getattr(eng.lib, name)(*args)
+    assert st == 0, f"{name} without {omit}: {st}: {eng.lib.fs_last_error(eng._ctx).decode()}"
+    if not host:
+        torch.cuda.synchronize()
+    return {k: held[k] if host else held[k].cpu().numpy() for k in results if k not in omit}
+
+
+def rx_pin_compare(kind, got, e, n):
+    """The full call's arrays against the restatement's dict: the written entries equal, the rest the
+    pattern."""
+    from seqs_amd.framesum import FLOW_TOTALS_DTYPE, TOTALS_DTYPE
+
+    t = got["totals"].view(TOTALS_DTYPE if kind == 0 else FLOW_TOTALS_DTYPE)[0]
+    fields = ("payload_bytes", "n_runs") + (("n_flows", "n_accepted") if kind >= 1 else ())
+    assert [int(t[f]) for f in fields] == [e[f] for f in fields] and int(t["reserved"]) == 0
+    written = dict(payload=e["payload"], runs=e["runs"], run_of=e["run_of"], out=e["dig"], status=e["st"])
+    if kind >= 1:
+        written.update(flows=e["flows"], order=e["order"])
+    if kind >= 2:
+        written.update(rings=e["rings"], socks_out=e["socks_out"], delivered=e["delivered"])
+    if kind == 3:
+        written.update(snd_out=e["snd_out"], code=e["code"])
+    assert set(written) | {"totals"} == set(got)
+    for k, want in written.items():
+        want = np.frombuffer(want.tobytes(), dtype=np.uint8)
+        assert np.array_equal(got[k][: want.size], want), (kind, k)
+        assert (got[k][want.size :] == 0xA5).all(), (kind, k)
+    assert e["runs"].size < n  # (some entries stay unwritten)
+
+
+def test_rx_calls_with_each_nullable_array_null(eng):
+    """Each of the eight RX entry points, once with every array passed (equal to the restatements of
+    tests/coalesce_ref.py, flows_ref.py, deliver_ref.py and recv_ref.py), once per nullable argument
+    with that argument NULL, and once with all of them NULL: every array that was passed, the rings
+    and the totals equal the full call's byte for byte, the unwritten entries included."""
+    case = rx_pin_case()
+    for kind in range(4):
+        nullable = [a for a, first in RX_NULLABLE if kind >= first]
+        for host in (False, True):
+            full = rx_pin_call(eng, kind, host, case)
+            rx_pin_compare(kind, full, case["expected"][kind], case["n"])
+            for omit in [(a,) for a in nullable] + [tuple(nullable)]:
+                got = rx_pin_call(eng, kind, host, case, omit)
+                assert set(got) == set(full) - set(omit)
+                for k, v in got.items():
+                    assert np.array_equal(v, full[k]), (RX_BASES[kind], host, omit, k)
