@@ -79,6 +79,18 @@ SND_OUT_DTYPE = np.dtype([("snd_una", "<u4"), ("snd_wnd", "<u4"), ("n_taken", "<
 RECV_ACK_OWED, RECV_FIN = 1, 2  # fs_rx_snd_out.flags
 # the per-frame codes of the receive call
 RECV_NONE, RECV_TAKEN, RECV_DUPLICATE, RECV_UNSENT, RECV_REJECTED, RECV_KEEPALIVE, RECV_RING_FULL = range(7)
+# The accept call (include/framesum_accept.h): fs_listener (24 bytes), fs_accept_slot (12), fs_accept_conn
+# (48) and fs_listener_out (16), none with padding
+LISTENER_DTYPE = np.dtype([("local", "u1", (6,)), ("mac", "u1", (6,)), ("slot_first", "<u4"), ("n_slots", "<u4"),
+                           ("reserved", "<u4")])
+ACCEPT_SLOT_DTYPE = np.dtype([("iss", "<u4"), ("rcv_wnd", "<u4"), ("ip_id", "<u2"), ("reserved", "<u2")])
+ACCEPT_CONN_DTYPE = np.dtype([("key", "u1", (13,)), ("used", "u1"), ("remote_mac", "u1", (6,)), ("peer_mss", "<u2"),
+                              ("reserved", "<u2"), ("frame", "<u4"), ("flow", "<u4"), ("irs", "<u4"), ("rcv_nxt", "<u4"),
+                              ("snd_nxt", "<u4"), ("snd_wnd", "<u4")])
+LISTENER_OUT_DTYPE = np.dtype([("n_syn", "<u4"), ("n_accepted", "<u4"), ("n_full", "<u4"), ("reserved", "<u4")])
+ACCEPT_STRIDE = 64
+ACCEPT_NONE, ACCEPT_FULL = 0xFFFFFFFF, 0xFFFFFFFE  # accept_of of a flow that is no candidate / found no slot
+ACCEPT_MAX_LISTENERS = ACCEPT_MAX_SLOTS = 65536
 # fs_tx_sock: one socket of the ring send (104 bytes, no padding), and fs_tx_sock_out (32 bytes)
 TX_SOCK_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("ring_off", "<u8"), ("ring_size", "<u4"),
                           ("ring_rpos", "<u4"), ("ring_buffered", "<u4"), ("snd_una", "<u4"), ("snd_nxt", "<u4"),
@@ -178,6 +190,18 @@ RECV_PROTOTYPES = {
                                        _p, _p, _p, _p, _p, _p, _p]),
 }
 
+# The functions include/framesum_accept.h declares (the fifth header), in its order: product symbols too.
+# The receive call's prototypes with listeners, n_listeners, slots, n_slots, synack_flags, conns,
+# listeners_out, accept_of, synacks, synack_out and synack_status behind `code`.
+ACCEPT_PROTOTYPES = {
+    "fs_accept_flows_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p,
+                                    _p, _u32, _p, _u32, _u32, _p, _p, _p, _p, _p, _p,
+                                    _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "fs_accept_flows_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p,
+                                         _p, _u32, _p, _u32, _u32, _p, _p, _p, _p, _p, _p,
+                                         _p, _u64, _p, _p, _p, _p, _p, _p, _p]),
+}
+
 # Not in the header, set only where the loaded library has them: the test library's hooks
 # (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
 OPTIONAL_PROTOTYPES = {
@@ -213,7 +237,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     if not os.path.exists(p):
         raise FramesumError(f"{p} is missing — run __graft_entry__.build() (or make -C seqs_amd/csrc)")
     lib = ctypes.CDLL(p)
-    tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **RECV_PROTOTYPES, **OPTIONAL_PROTOTYPES}
+    tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **RECV_PROTOTYPES, **ACCEPT_PROTOTYPES,
+              **OPTIONAL_PROTOTYPES}
     for name, (restype, argtypes) in tables.items():
         if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
             continue

@@ -1,4 +1,4 @@
-// framesum C ABI -- the four RX call kinds, each with a device form and a host form:
+// framesum C ABI -- the five RX call kinds, each with a device form and a host form:
 //   the plain coalesce       fs_coalesce_batch, fs_coalesce_batch_host (include/framesum.h;
 //                            kernels: framesum_coalesce.hip)
 //   the flow-aware coalesce  fs_coalesce_flows_batch, ..._host (framesum_flows.hip)
@@ -6,6 +6,9 @@
 //                            framesum_deliver.hip): the flow call, then the delivery into socket rings
 //   the receive call         fs_recv_flows_batch, ..._host (include/framesum_recv.h; framesum_recv.hip):
 //                            the delivery, then the fold of every listed socket's ACKs and windows
+//   the accept call          fs_accept_flows_batch, ..._host (include/framesum_accept.h;
+//                            framesum_accept.hip): the receive call, then the passive open of every first
+//                            SYN to a listener, with its SYN-ACK
 // A call is one record (RxCall) that the entry point fills from its flat arguments; the checks, the
 // stages up to the call's kind and the one host form all read that record.
 #include <algorithm>
@@ -13,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "framesum_accept.h"
 #include "framesum_ctx.h"
 #include "framesum_deliver.h"
 #include "framesum_flows.h"
@@ -26,8 +30,18 @@ using framesum::RxResults;
 namespace rxp = framesum::plan::rx;
 namespace dl = framesum::deliver;
 namespace rv = framesum::recv;
+namespace ac = framesum::accept;
 
 namespace {
+
+// The listening part of an accept call: the caller's lists, where its own results go (x: the caller's
+// pointers, host or device as the form has them), and the listener table check_accept builds.
+struct RxListen {
+    const fs_listener* listeners = nullptr;
+    const fs_accept_slot* slots = nullptr;
+    framesum::RxAccept x{};
+    std::vector<uint32_t> table;
+};
 
 // The socket part of a delivery or a receive call: the caller's lists, and what check_socks makes of
 // them (the socket table, the span of `rings` the listed rings cover).
@@ -46,6 +60,7 @@ struct RxCall {
     RxBatch b;
     RxResults r{};
     RxSocks s;
+    RxListen l;
     RxCall(rxp::Kind kind_, const char* fn_, const RxBatch& b_) : kind(kind_), fn(fn_), b(b_) {}
     // the flat arguments, group by group as the ABI lists them
     void coalesce(uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, void* totals, fs_digest* out,
@@ -62,6 +77,13 @@ struct RxCall {
     void send_side(const fs_rx_snd* snd, fs_rx_snd_out* snd_out, uint8_t* code) {
         s.snd = snd, r.array[rxp::kSndOut] = snd_out, r.array[rxp::kCode] = code;
     }
+    void listening(const fs_listener* listeners, uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots,
+                   uint32_t synack_flags, fs_accept_conn* conns, fs_listener_out* listeners_out, uint32_t* accept_of,
+                   uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status) {
+        l.listeners = listeners, l.slots = slots;
+        l.x = framesum::RxAccept{s.n_socks, n_listeners, n_slots, synack_flags, conns, listeners_out,
+                                 accept_of,  synacks,     synack_out, synack_status};
+    }
 };
 // The call as the launches see it: in the device forms the caller's batch and arrays on the caller's
 // stream, in the host forms the staged batch and the context's device arrays on the compute stream.
@@ -69,6 +91,7 @@ struct RxDevice {
     RxBatch b;
     RxResults r;
     hipStream_t stream;
+    framesum::RxAccept x{};  // (the accept call only)
 };
 
 fs_status invalid(fs_ctx* ctx, const RxCall& c, const std::string& what) {
@@ -97,9 +120,17 @@ fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
         if (s.span.bad != dl::kGood)
             return invalid(ctx, c, "socket " + std::to_string(s.span.sock) + ": " + dl::bad_text(s.span.bad));
     }
-    if (c.kind == rxp::kRecv) {
+    if (c.kind >= rxp::kRecv) {
         const rv::CheckSnd cs = rv::check_snd(c.s.socks, c.s.snd, c.s.n_socks, c.r.snd_out() != nullptr);
         if (cs.bad != rv::kSndGood) return invalid(ctx, c, "socket " + std::to_string(cs.sock) + ": " + rv::bad_snd_text(cs.bad));
+    }
+    if (c.kind == rxp::kAccept) {  // the listener and slot lists' checks (framesum_accept.h), which also build the table
+        RxListen& l = c.l;
+        const ac::CheckAccept ca =
+            ac::check_accept(l.listeners, l.x.n_listeners, l.slots, l.x.n_slots, l.x.synack_flags, l.x.conns != nullptr,
+                             l.x.listeners_out != nullptr, l.x.synacks != nullptr, ctx->flow_hash_mask, l.table);
+        if (ca.bad != ac::kAcceptGood)
+            return invalid(ctx, c, "listener or slot " + std::to_string(ca.index) + ": " + ac::bad_accept_text(ca.bad));
     }
     return FS_SUCCESS;
 }
@@ -184,6 +215,35 @@ fs_status recv_stage(fs_ctx* ctx, const RxSocks& s, const RxDevice& d, const RxL
     return staged_launch(ctx, (uint64_t)s.n_socks * sizeof(rv::Sock), d.stream, "fs_recv_flows_batch: launch", fill, kernels);
 }
 
+// `conns` and `listeners_out` zeroed and `accept_of` set to "none"; then, for a non-empty batch with
+// listeners, the listener block staged in a block of its own and the accept kernels.
+fs_status accept_stage(fs_ctx* ctx, const RxListen& l, const RxDevice& d, const RxLaunch& how, RxLeft& left) {
+    const framesum::RxAccept& x = d.x;
+    if (x.n_slots != 0) FS_HIP(ctx, hipMemsetAsync(x.conns, 0, (uint64_t)x.n_slots * sizeof(fs_accept_conn), d.stream));
+    if (x.n_listeners != 0)
+        FS_HIP(ctx, hipMemsetAsync(x.listeners_out, 0, (uint64_t)x.n_listeners * sizeof(fs_listener_out), d.stream));
+    if (d.b.n != 0 && x.accept_of) FS_HIP(ctx, hipMemsetAsync(x.accept_of, 0xFF, 4ull * d.b.n, d.stream));
+    if (d.b.n == 0 || x.n_listeners == 0) return FS_SUCCESS;
+    left.acs = framesum::accept_scratch(d.b.n, x.n_listeners, x.n_slots);
+    if (left.acs.sort_bytes == 0)
+        return set_err(ctx, FS_E_HIP, "fs_accept_flows_batch: the sort reports no temporary storage size");
+    fs_status st = ctx->ac_scratch.grow(ctx, left.acs.bytes);
+    if (st == FS_SUCCESS) st = seg_tables(ctx);
+    if (st != FS_SUCCESS) return st;
+    left.accept_scratch = ctx->ac_scratch.p;
+    // the SYN-ACK kernel's grid as the TX frame build caps it: two workgroups per CU (their tables fit its
+    // LDS twice) unless fs_ctx_set_workgroups asks for fewer
+    const int tx_wgs = ctx->workgroups > 0 && ctx->workgroups < 2 * ctx->num_cus ? ctx->workgroups : 2 * ctx->num_cus;
+    const ac::Block blk = ac::block_of(x.n_listeners, x.n_slots);
+    const auto fill = [&](uint8_t* h_block) {
+        ac::stage(l.listeners, x.n_listeners, l.table.data(), l.slots, x.n_slots, blk, h_block);
+    };
+    const auto kernels = [&](const uint8_t* d_block) {
+        return framesum::launch_accept(d.b, x, left, d_block, ctx->d_seg_tables, tx_wgs, how);
+    };
+    return staged_launch(ctx, blk.bytes, d.stream, "fs_accept_flows_batch: launch", fill, kernels);
+}
+
 // The stages up to the call's kind. An empty batch has zero totals in place of its gather; the socket
 // calls still run their walks then. `left`: what the stages left (`copied`: non-empty batches only).
 fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
@@ -195,7 +255,8 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
     else
         st = c.kind == rxp::kPlain ? plain_stage(ctx, d, how, left) : flows_stage(ctx, d, how, left);
     if (st == FS_SUCCESS && c.kind >= rxp::kDeliver) st = deliver_stage(ctx, c.s, d, how, left);
-    if (st == FS_SUCCESS && c.kind == rxp::kRecv) st = recv_stage(ctx, c.s, d, how, left);
+    if (st == FS_SUCCESS && c.kind >= rxp::kRecv) st = recv_stage(ctx, c.s, d, how, left);
+    if (st == FS_SUCCESS && c.kind == rxp::kAccept) st = accept_stage(ctx, c.l, d, how, left);
     return st;
 }
 
@@ -203,7 +264,7 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
 fs_status rx_device(fs_ctx* ctx, const RxCall& c, void* stream) {
     FS_HIP(ctx, hipSetDevice(ctx->device));
     RxLeft left;
-    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream)}, left);
+    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.x}, left);
 }
 
 // A checked host form: the batch staged through slot 0, the result arrays carved from the context's
@@ -218,10 +279,18 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     if (n == 0) {  // nothing for a device to do: the sockets keep their state
         std::memset(h.totals(), 0, totals_bytes);
         for (uint32_t i = 0; sockets && i < s.n_socks; ++i) h.socks_out()[i] = dl::untouched(s.socks[i]);
-        for (uint32_t i = 0; c.kind == rxp::kRecv && i < s.n_socks; ++i)
+        for (uint32_t i = 0; c.kind >= rxp::kRecv && i < s.n_socks; ++i)
             h.snd_out()[i] = rv::untouched(s.snd[i].snd_una, s.snd[i].snd_wnd);
+        if (c.kind == rxp::kAccept) {  // no slot is filled, no listener has a candidate
+            if (c.l.x.n_slots) std::memset(c.l.x.conns, 0, (uint64_t)c.l.x.n_slots * sizeof(fs_accept_conn));
+            if (c.l.x.n_listeners) std::memset(c.l.x.listeners_out, 0, (uint64_t)c.l.x.n_listeners * sizeof(fs_listener_out));
+        }
         return FS_SUCCESS;
     }
+    // the accept call's own arrays, as the caller passed them, in plan::rx::AcceptArray's order
+    const bool accepts = c.kind == rxp::kAccept;
+    const framesum::RxAccept& hx = c.l.x;
+    void* const h_accept[rxp::kAcceptArrays] = {hx.conns, hx.listeners_out, hx.accept_of, hx.synacks, hx.synack_out, hx.synack_status};
     const framesum::plan::Scan sc = framesum::plan::scan_batch(b.offsets, b.lengths, n, frames_bytes);
     if (sc.bad < n) return invalid(ctx, c, "frame " + std::to_string(sc.bad) + " ends past frames_bytes");
     // the device payload buffer: payload_cap, or the most payload the batch can hold when that is less
@@ -229,13 +298,14 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     // the rings' span (the kernels address ring bytes at base + ring_off)
     const uint64_t span = s.span.hi - s.span.lo;
     const rxp::Layout L = rxp::layout(c.kind, n, s.n_socks);
+    const rxp::AcceptLayout AL = rxp::accept_layout(L.bytes, n, hx.n_listeners, hx.n_slots);
     fs_status st = begin_host_call(ctx);
     if (st == FS_SUCCESS && sockets) st = ctx->dl_rings.grow(ctx, span);
     // (the socket calls begin once more, behind the rings' buffer: a second hipSetDevice that keeps their
     // sequence of HIP calls what profiles/rx_call_refactor/calls.txt compares)
     if (st == FS_SUCCESS && sockets) st = begin_host_call(ctx);
     if (st == FS_SUCCESS) st = ctx->co_payload.grow(ctx, d_cap);
-    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, L.bytes);
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, accepts ? AL.bytes : L.bytes);
     if (st != FS_SUCCESS) return st;
     Staged sg;
     st = stage_batch(ctx, b.frames, frames_bytes, sc.lo, sc.hi, b.offsets, b.lengths, n, sg);
@@ -247,6 +317,22 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     for (uint32_t a = 0; a < rxp::kArrays; ++a) d.r.array[a] = h.array[a] && L.has((rxp::Array)a) ? ctx->rx_arrays.p + L.at[a] : nullptr;
     // the span goes in first, so that the copy back returns the caller's own bytes between the rings
     if (span != 0) FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->dl_rings.p, h.rings + s.span.lo, span, hipMemcpyHostToDevice, sg.ks));
+    // the accept call's arrays likewise; those of which the call writes the filled slots' entries only go
+    // in first, so that the whole array comes back with the caller's bytes elsewhere
+    void* d_accept[rxp::kAcceptArrays] = {};
+    for (uint32_t a = 0; accepts && a < rxp::kAcceptArrays; ++a) {
+        if (!h_accept[a] || AL.room[a] == 0) continue;
+        d_accept[a] = ctx->rx_arrays.p + AL.at[a];
+        if (rxp::kAcceptArrayDesc[a].goes_in)
+            FS_HIP_DRAIN(ctx, hipMemcpyAsync(d_accept[a], h_accept[a], AL.room[a], hipMemcpyHostToDevice, sg.ks));
+    }
+    d.x = framesum::RxAccept{hx.n_socks, hx.n_listeners, hx.n_slots, hx.synack_flags,
+                             static_cast<fs_accept_conn*>(d_accept[rxp::kConns]),
+                             static_cast<fs_listener_out*>(d_accept[rxp::kListenersOut]),
+                             static_cast<uint32_t*>(d_accept[rxp::kAcceptOf]),
+                             static_cast<uint8_t*>(d_accept[rxp::kSynacks]),
+                             static_cast<fs_digest*>(d_accept[rxp::kSynackOut]),
+                             static_cast<uint8_t*>(d_accept[rxp::kSynackStatus])};
     RxLeft left;
     st = rx_run(ctx, c, d, left);
     if (st != FS_SUCCESS) {
@@ -274,6 +360,8 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     FS_HIP_DRAIN(ctx, back(h.payload, ctx->co_payload.p, copied));
     for (uint32_t a = rxp::kTotals + 1; a < rxp::kArrays; ++a)
         FS_HIP_DRAIN(ctx, back(h.array[a], d.r.array[a], rxp::bytes_back(c.kind, (rxp::Array)a, n, s.n_socks, got)));
+    for (uint32_t a = 0; accepts && a < rxp::kAcceptArrays; ++a)
+        FS_HIP_DRAIN(ctx, back(d_accept[a] ? h_accept[a] : nullptr, d_accept[a], AL.room[a]));
     FS_HIP_DRAIN(ctx, back(s.n_socks ? h.rings + s.span.lo : nullptr, ctx->dl_rings.p, span));
     FS_HIP_DRAIN(ctx, back(h.out, sg.d_out, (uint64_t)n * sizeof(fs_digest)));
     FS_HIP_DRAIN(ctx, back(h.status, sg.d_st, n));
@@ -400,6 +488,52 @@ fs_status fs_recv_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t 
     c.flows(flows, order);
     c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
     c.send_side(snd, snd_out, code);
+    const fs_status st = rx_check(ctx, c, false);
+    return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
+}
+
+fs_status fs_accept_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                                uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
+                                uint8_t* rings, uint64_t rings_bytes, fs_rx_sock_out* socks_out, uint8_t* delivered,
+                                const fs_rx_snd* snd, fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                                uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots, uint32_t synack_flags,
+                                fs_accept_conn* conns, fs_listener_out* listeners_out, uint32_t* accept_of,
+                                uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status, uint8_t* payload,
+                                uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order,
+                                uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kAccept, "fs_accept_flows_batch", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
+    const fs_status st = rx_check(ctx, c, true);
+    return st != FS_SUCCESS ? st : rx_device(ctx, c, stream);
+}
+
+fs_status fs_accept_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                                     const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags,
+                                     const fs_rx_sock* socks, uint32_t n_socks, uint8_t* rings, uint64_t rings_bytes,
+                                     fs_rx_sock_out* socks_out, uint8_t* delivered, const fs_rx_snd* snd,
+                                     fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                                     uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots,
+                                     uint32_t synack_flags, fs_accept_conn* conns, fs_listener_out* listeners_out,
+                                     uint32_t* accept_of, uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status,
+                                     uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows,
+                                     uint32_t* order, uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out,
+                                     uint8_t* status) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kAccept, "fs_accept_flows_batch_host", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
     const fs_status st = rx_check(ctx, c, false);
     return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
 }

@@ -9,6 +9,7 @@
 #include "../../include/framesum.h"
 #include "../../include/framesum_deliver.h"
 #include "../../include/framesum_recv.h"
+#include "../../include/framesum_accept.h"
 #include "framesum_choice.h"
 #include "framesum_plan.h"
 
@@ -98,10 +99,10 @@ hipError_t launch_send_rings(const uint8_t* d_block, const segment::Block& b, ui
                              uint8_t* status, uint32_t mtu, uint32_t flags, uint32_t align, const SegTables* tables,
                              int workgroups, hipStream_t stream);
 
-// ---- The RX calls (framesum_coalesce.hip, framesum_flows.hip, framesum_deliver.hip, framesum_recv.hip).
-// A call is a row of stages on one stream -- the digest launch and the plain or the flow-aware gather,
-// then the delivery, then the receive call's fold -- each behind the one before it and reading what it
-// left. The launches take the call as a few records.
+// ---- The RX calls (framesum_coalesce.hip, framesum_flows.hip, framesum_deliver.hip, framesum_recv.hip,
+// framesum_accept.hip). A call is a row of stages on one stream -- the digest launch and the plain or the
+// flow-aware gather, then the delivery, then the receive call's fold, then the accept call's passive open
+// -- each behind the one before it and reading what it left. The launches take the call as a few records.
 
 // The batch as the launches read it.
 struct RxBatch {
@@ -161,10 +162,29 @@ struct DeliverScratch {
 struct RecvScratch {
     uint64_t aw, bytes;
 };
+// AcceptScratch: 256-byte aligned like FlowScratch (accept_scratch asks the sort for its temporary
+// storage's size too); 20 bytes per frame and 88 per slot beside it.
+struct AcceptScratch {
+    uint64_t rank_in, rank_sorted, synrec, cand_frame, sort_temp, sort_bytes, bytes;
+};
 CoScratch coalesce_scratch(uint32_t n);
 FlowScratch flows_scratch(uint32_t n);
 DeliverScratch deliver_scratch(uint32_t n, uint32_t n_socks);
 RecvScratch recv_scratch(uint32_t n);
+AcceptScratch accept_scratch(uint32_t n, uint32_t n_listeners, uint32_t n_slots);
+
+// What the accept call has beside a receive call's batch and results: the counts of its staged lists and
+// where its own results go on the device (the caller's pointers in the device form, the context's device
+// arrays in the host form; accept_of, synack_out and synack_status are nullable).
+struct RxAccept {
+    uint32_t n_socks, n_listeners, n_slots, synack_flags;
+    fs_accept_conn* conns;
+    fs_listener_out* listeners_out;
+    uint32_t* accept_of;
+    uint8_t* synacks;
+    fs_digest* synack_out;
+    uint8_t* synack_status;
+};
 
 // What the stages of one call leave on the device for the stages behind them: each stage's scratch, laid
 // out as its layout says (all zero for a stage that has not run: an empty batch has no flow stage), and
@@ -177,6 +197,8 @@ struct RxLeft {
     DeliverScratch ds;
     uint8_t* recv_scratch;
     RecvScratch rs;
+    uint8_t* accept_scratch;
+    AcceptScratch acs;
 };
 
 // The launches that follow a batch's digest launch on the stream (fs_coalesce_batch in
@@ -198,5 +220,13 @@ hipError_t launch_deliver(const RxBatch& b, const RxResults& r, const RxLeft& le
 // With n of 0 only the sockets' out records are written.
 hipError_t launch_recv(const RxBatch& b, const RxResults& r, const RxLeft& left, const uint8_t* d_block, uint32_t n_socks,
                        const RxLaunch& how);
+// The launches that follow a non-empty batch's receive launches (fs_accept_flows_batch in
+// include/framesum_accept.h) and read what the flow and, with sockets listed, the delivery launches left.
+// `d_block`: the device copy of the staged block (framesum_accept.h block_of: the listeners, their table,
+// the slots; at least one listener). `tables`: the TX frame build's, and `tx_workgroups` the cap of the
+// SYN-ACK kernel's grid as that build has it. x.conns, x.listeners_out and x.accept_of are set to their
+// "nothing" values by the caller.
+hipError_t launch_accept(const RxBatch& b, const RxAccept& x, const RxLeft& left, const uint8_t* d_block,
+                         const SegTables* tables, int tx_workgroups, const RxLaunch& how);
 
 }  // namespace framesum

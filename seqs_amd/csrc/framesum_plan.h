@@ -217,15 +217,16 @@ inline void host_chunks(const uint64_t* offsets, const uint32_t* lengths, uint32
 }
 
 // ---------------------------------------------------------------------------------------
-// The device result arrays of the four RX host forms (fs_coalesce_batch_host,
-// fs_coalesce_flows_batch_host, fs_deliver_flows_batch_host, fs_recv_flows_batch_host), described
+// The device result arrays of the five RX host forms (fs_coalesce_batch_host,
+// fs_coalesce_flows_batch_host, fs_deliver_flows_batch_host, fs_recv_flows_batch_host and, with the
+// arrays of its own in the second table below, fs_accept_flows_batch_host), described
 // once: which arrays a call kind has, what each is sized by, where each lies in the context's one
 // buffer, and how much of each comes back given the totals the device reported. The host forms carve
 // the buffer and copy back by walking this description (framesum_api_rx.cpp).
 namespace rx {
 
 // A kind has the arrays of the kinds before it and its own.
-enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv };
+enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv, kAccept };
 enum Array : uint32_t { kTotals, kRuns, kFlowRecs, kOrder, kRunOf, kDelivered, kSocksOut, kSndOut, kCode, kArrays };
 // What counts an array's entries: one record, the batch's frames, the call's sockets, or (for what
 // comes back only) one of the totals.
@@ -288,6 +289,43 @@ inline Layout layout(Kind kind, uint64_t n, uint64_t n_socks) {
 // The bytes of array `a` that come back to the caller, given consistent totals `t`.
 constexpr uint64_t bytes_back(Kind kind, Array a, uint64_t n, uint64_t n_socks, const Totals& t) {
     return kind < kArrayDesc[a].from ? 0 : elem_bytes(kind, a) * count_of(kArrayDesc[a].back, n, n_socks, t);
+}
+
+// The fifth kind's own arrays (fs_accept_flows_batch_host: the kind has every array above, and these),
+// described the same way in a table of their own: what counts an array's entries, where each lies behind
+// the arrays above in the same buffer, and whether the caller's bytes go to the device first (the call
+// writes only the filled slots' entries of those, and every array comes back whole).
+enum AcceptArray : uint32_t { kConns, kListenersOut, kAcceptOf, kSynacks, kSynackOut, kSynackStatus, kAcceptArrays };
+enum AcceptCount : uint32_t { kPerSlot, kPerListener, kPerFrameOfBatch };
+struct AcceptArrayDesc {
+    uint32_t elem, align;  // bytes per entry, and the alignment the kernels' stores want
+    AcceptCount count;
+    bool goes_in;
+};
+constexpr AcceptArrayDesc kAcceptArrayDesc[kAcceptArrays] = {
+    {48, 4, kPerSlot, false},          // fs_accept_conn
+    {16, 4, kPerListener, false},      // fs_listener_out
+    {4, 4, kPerFrameOfBatch, false},   // accept_of
+    {64, 1, kPerSlot, true},           // synacks (FS_ACCEPT_STRIDE)
+    {8, 8, kPerSlot, true},            // synack_out
+    {1, 1, kPerSlot, true},            // synack_status
+};
+struct AcceptLayout {
+    uint64_t at[kAcceptArrays], room[kAcceptArrays], bytes;  // `bytes`: the arrays above and these
+};
+// `base`: layout(kAccept, n, n_socks).bytes.
+inline AcceptLayout accept_layout(uint64_t base, uint64_t n, uint64_t n_listeners, uint64_t n_slots) {
+    AcceptLayout L;
+    uint64_t at = base;
+    for (uint32_t a = 0; a < kAcceptArrays; ++a) {
+        const AcceptArrayDesc& d = kAcceptArrayDesc[a];
+        at = (at + d.align - 1) / d.align * d.align;
+        L.at[a] = at;
+        L.room[a] = d.elem * (d.count == kPerSlot ? n_slots : d.count == kPerListener ? n_listeners : n);
+        at += L.room[a];
+    }
+    L.bytes = at;
+    return L;
 }
 
 }  // namespace rx

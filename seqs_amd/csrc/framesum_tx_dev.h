@@ -329,18 +329,24 @@ __device__ __forceinline__ void build_frame(const Args<typename Src::Rec>& a, co
     }
 }
 
-// A whole kernel: the tables into LDS, then every wave builds its tiles' frames back to back.
-template <typename Src>
-__device__ __forceinline__ void build_frames(const Args<typename Src::Rec>& a) {
-    // the tables, from their basis: entry v of a table is the XOR of the basis entries of v's bits
+// The tables into LDS, from their basis: entry v of a table is the XOR of the basis entries of v's bits.
+// Every kernel that runs build_frame starts with this (the accept call's SYN-ACK kernel too,
+// framesum_accept.hip).
+__device__ __forceinline__ void load_tables(const SegTables* tables) {
     for (uint32_t e = threadIdx.x; e < kSegTableCount * 1024u; e += kThreads) {
-        const uint32_t* basis = &a.tables->basis[0][0][0] + (e >> 8) * 8;
+        const uint32_t* basis = &tables->basis[0][0][0] + (e >> 8) * 8;
         uint32_t r = 0;
 #pragma unroll
         for (int jb = 0; jb < 8; ++jb) r ^= (e & (1u << jb)) ? basis[jb] : 0u;
         g_z[e] = r;
     }
     __syncthreads();
+}
+
+// A whole kernel: the tables into LDS, then every wave builds its tiles' frames back to back.
+template <typename Src>
+__device__ __forceinline__ void build_frames(const Args<typename Src::Rec>& a) {
+    load_tables(a.tables);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t n_tiles = (a.n_frames + a.tile - 1) / a.tile;

@@ -21,6 +21,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .abi import (  # noqa: F401 (re-exported: this module is the binding's public face)
+    ACCEPT_CONN_DTYPE, ACCEPT_FULL, ACCEPT_MAX_LISTENERS, ACCEPT_MAX_SLOTS, ACCEPT_NONE, ACCEPT_PROTOTYPES, ACCEPT_SLOT_DTYPE,
+    ACCEPT_STRIDE, LISTENER_DTYPE, LISTENER_OUT_DTYPE,
     DELIVER_MAX_SOCKS, DELIVER_PROTOTYPES, DIGEST_DTYPE, EXPORTED_SYMBOLS, FCS_APPEND, FILL_CSUM, FLOW_DTYPE,
     FLOW_TOTALS_DTYPE, FS_E_HIP, FS_E_INVALID, FS_E_NODEVICE, FS_E_NOMEM, FS_ERR_FCS, FS_SUCCESS, NO_FLOW, NO_RUN,
     PROTOTYPES, RECV_ACK_OWED, RECV_DUPLICATE, RECV_FIN, RECV_KEEPALIVE, RECV_NONE, RECV_PROTOTYPES, RECV_REJECTED,
@@ -83,6 +85,7 @@ _RX_FLOWS = ("fs_coalesce_flows_batch", FLOW_TOTALS_DTYPE,
              ((FLOW_DTYPE, "n_flows"), (np.dtype(np.uint32), "n_accepted")))
 _RX_DELIVER = ("fs_deliver_flows_batch", *_RX_FLOWS[1:])
 _RX_RECV = ("fs_recv_flows_batch", *_RX_FLOWS[1:])  # (the delivery call with snd, snd_out and code behind delivered)
+_RX_ACCEPT = ("fs_accept_flows_batch", *_RX_FLOWS[1:])  # (the receive call with the listening arguments behind code)
 
 
 @dataclass
@@ -555,6 +558,113 @@ class Engine(_Handle):
         return (snd_out, codes, socks_out, marks,
                 *self._rx_host(_RX_RECV, frames, offsets, lengths, mtu, flags, payload, args))
 
+    # ---- the accept call: the receive call plus the passive open (include/framesum_accept.h) ----
+    def accept_flows_device(self, frames, offsets, lengths, socks: np.ndarray, snd: np.ndarray, rings,
+                            listeners: np.ndarray, slots: np.ndarray, mtu: int = 0, flags: int = 0, synack_flags: int = 0,
+                            payload=None, delivered: bool = True, code: bool = True, accept_of: bool = True,
+                            synacks=None, synack_results: bool = True, stream=None):
+        """recv_flows_device plus the passive open of every flow without a listed socket whose first
+        frame is a SYN to a listener (fs_accept_flows_batch): `listeners` is a LISTENER_DTYPE array on the
+        host (local address and port in wire order, the SYN-ACKs' source MAC, the listener's range of
+        `slots`), `slots` an ACCEPT_SLOT_DTYPE array on the host (iss, rcv_wnd and the IPv4 ID seed of each
+        free connection). A listener's candidates take its slots in ascending order of flow number.
+        `synacks`: a uint8 CUDA tensor of n_slots * ACCEPT_STRIDE bytes (else a new zeroed one), of which
+        only the 54 (58 with synack_flags FCS_APPEND) frame bytes of filled slots are written. Returns
+        (conns, listeners_out, accept_of, synacks, synack_out, synack_status, then recv_flows_device's
+        tuple) device tensors: conns (n_slots, 48) uint8 = ACCEPT_CONN_DTYPE records, listeners_out
+        (n_listeners, 16) uint8 = LISTENER_OUT_DTYPE records, accept_of (n,) int32 per flow (the slot,
+        -2 = ACCEPT_FULL, -1 = ACCEPT_NONE; None when `accept_of` is False), synack_out (n_slots, 2) int32
+        and synack_status (n_slots,) uint8 as digest_device gives them, written for filled slots only
+        (zeroed here first; None when `synack_results` is False; the caller's own pair of tensors when it
+        is a tuple, whose other entries keep their values). Asynchronous on `stream`; split_accept()
+        brings the records to the host."""
+        import torch
+
+        socks = np.ascontiguousarray(socks, dtype=SOCK_DTYPE)
+        snd = np.ascontiguousarray(snd, dtype=SND_DTYPE)
+        listeners = np.ascontiguousarray(listeners, dtype=LISTENER_DTYPE)
+        slots = np.ascontiguousarray(slots, dtype=ACCEPT_SLOT_DTYPE)
+        assert snd.size == socks.size, "one send-side record per socket"
+        n, dev = int(lengths.numel()), frames.device
+        n_slots, n_listeners = int(slots.size), int(listeners.size)
+        assert rings.is_cuda and rings.dtype == torch.uint8 and rings.is_contiguous()
+        if synacks is None:
+            synacks = torch.zeros((n_slots * ACCEPT_STRIDE,), dtype=torch.uint8, device=dev)
+        assert synacks.is_cuda and synacks.dtype == torch.uint8 and synacks.is_contiguous()
+        assert synacks.numel() >= n_slots * ACCEPT_STRIDE, "synacks holds ACCEPT_STRIDE bytes per slot"
+        socks_out = torch.empty((int(socks.size), SOCK_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        snd_out = torch.empty((int(socks.size), SND_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        marks = torch.empty((n,), dtype=torch.uint8, device=dev) if delivered else None
+        codes = torch.empty((n,), dtype=torch.uint8, device=dev) if code else None
+        conns = torch.empty((n_slots, ACCEPT_CONN_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        listeners_out = torch.empty((n_listeners, LISTENER_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        of = torch.empty((n,), dtype=torch.int32, device=dev) if accept_of else None
+        if isinstance(synack_results, tuple):  # the caller's own (n_slots, 2) int32 and (n_slots,) uint8 tensors
+            syn_out, syn_st = synack_results
+            assert syn_out.is_cuda and syn_out.dtype == torch.int32 and syn_out.numel() == 2 * n_slots
+            assert syn_st.is_cuda and syn_st.dtype == torch.uint8 and syn_st.numel() == n_slots
+        else:
+            syn_out = torch.zeros((n_slots, 2), dtype=torch.int32, device=dev) if synack_results else None
+            syn_st = torch.zeros((n_slots,), dtype=torch.uint8, device=dev) if synack_results else None
+
+        def ptr(t):
+            return _tensor_ptr(t) if t is not None and t.numel() else None
+
+        args = (_array_ptr(socks), int(socks.size), _tensor_ptr(rings), rings.numel(), _tensor_ptr(socks_out),
+                ptr(marks), _array_ptr(snd), _tensor_ptr(snd_out), ptr(codes),
+                _array_ptr(listeners), n_listeners, _array_ptr(slots), n_slots, synack_flags, ptr(conns), ptr(listeners_out),
+                ptr(of), ptr(synacks), ptr(syn_out), ptr(syn_st))
+        return (conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
+                *self._rx_device(_RX_ACCEPT, frames, offsets, lengths, mtu, flags, payload, stream, args))
+
+    def accept_flows_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, socks: np.ndarray,
+                          snd: np.ndarray, rings: np.ndarray, listeners: np.ndarray, slots: np.ndarray, mtu: int = 0,
+                          flags: int = 0, synack_flags: int = 0, payload=None, delivered: bool = True, code: bool = True,
+                          accept_of: bool = True, synacks=None, synack_results: bool = True):
+        """accept_flows_device from and to host memory (fs_accept_flows_batch_host). `synacks`: a
+        writable uint8 array of n_slots * ACCEPT_STRIDE bytes (else a new zeroed one), written in place in
+        the frame bytes of filled slots only. Returns (conns ACCEPT_CONN_DTYPE[n_slots], listeners_out
+        LISTENER_OUT_DTYPE[n_listeners], accept_of uint32[n] or None, synacks, synack_out
+        DIGEST_DTYPE[n_slots] or None, synack_status uint8[n_slots] or None, then recv_flows_host's
+        tuple)."""
+        socks = np.ascontiguousarray(socks, dtype=SOCK_DTYPE)
+        snd = np.ascontiguousarray(snd, dtype=SND_DTYPE)
+        listeners = np.ascontiguousarray(listeners, dtype=LISTENER_DTYPE)
+        slots = np.ascontiguousarray(slots, dtype=ACCEPT_SLOT_DTYPE)
+        assert snd.size == socks.size, "one send-side record per socket"
+        assert isinstance(rings, np.ndarray) and rings.dtype == np.uint8 and rings.flags["C_CONTIGUOUS"]
+        assert rings.flags["WRITEABLE"], "accept_flows_host writes into `rings`"
+        n = int(np.asarray(lengths).size)
+        n_slots, n_listeners = int(slots.size), int(listeners.size)
+        if synacks is None:
+            synacks = np.zeros(n_slots * ACCEPT_STRIDE, dtype=np.uint8)
+        assert isinstance(synacks, np.ndarray) and synacks.dtype == np.uint8 and synacks.flags["C_CONTIGUOUS"]
+        assert synacks.flags["WRITEABLE"] and synacks.size >= n_slots * ACCEPT_STRIDE
+        socks_out = np.zeros(int(socks.size), dtype=SOCK_OUT_DTYPE)
+        snd_out = np.zeros(int(socks.size), dtype=SND_OUT_DTYPE)
+        marks = np.zeros(n, dtype=np.uint8) if delivered else None
+        codes = np.zeros(n, dtype=np.uint8) if code else None
+        conns = np.zeros(n_slots, dtype=ACCEPT_CONN_DTYPE)
+        listeners_out = np.zeros(n_listeners, dtype=LISTENER_OUT_DTYPE)
+        of = np.full(n, ACCEPT_NONE, dtype=np.uint32) if accept_of else None
+        if isinstance(synack_results, tuple):  # the caller's own DIGEST_DTYPE[n_slots] and uint8[n_slots] arrays
+            syn_out, syn_st = synack_results
+            assert syn_out.dtype == DIGEST_DTYPE and syn_out.size == n_slots and syn_out.flags["C_CONTIGUOUS"]
+            assert syn_st.dtype == np.uint8 and syn_st.size == n_slots and syn_st.flags["C_CONTIGUOUS"]
+        else:
+            syn_out = np.zeros(n_slots, dtype=DIGEST_DTYPE) if synack_results else None
+            syn_st = np.zeros(n_slots, dtype=np.uint8) if synack_results else None
+
+        def ptr(a):
+            return _array_ptr(a) if a is not None and a.size else None
+
+        args = (_array_ptr(socks), int(socks.size), _array_ptr(rings), rings.nbytes, _array_ptr(socks_out),
+                ptr(marks), _array_ptr(snd), _array_ptr(snd_out), ptr(codes),
+                _array_ptr(listeners), n_listeners, _array_ptr(slots), n_slots, synack_flags, ptr(conns), ptr(listeners_out),
+                ptr(of), ptr(synacks), ptr(syn_out), ptr(syn_st))
+        return (conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
+                *self._rx_host(_RX_ACCEPT, frames, offsets, lengths, mtu, flags, payload, args))
+
     # ---- TCP segments from socket TX rings (include/framesum_send.h) ------------
     @staticmethod
     def send_rings_layout(socks: np.ndarray, flags: int = 0, align: int = 1):
@@ -803,6 +913,65 @@ def split_socks(socks_out) -> np.ndarray:
 def split_snd(snd_out) -> np.ndarray:
     """The host view of recv_flows_device's `snd_out` tensor (this waits for it): SND_OUT_DTYPE[n_socks]."""
     return _records(snd_out, SND_OUT_DTYPE)
+
+
+def split_accept(conns, listeners_out, accept_of=None):
+    """The host view of accept_flows_device's `conns`, `listeners_out` and `accept_of` tensors (this waits
+    for them): (ACCEPT_CONN_DTYPE[n_slots], LISTENER_OUT_DTYPE[n_listeners], uint32[n] or None)."""
+    return (_records(conns, ACCEPT_CONN_DTYPE), _records(listeners_out, LISTENER_OUT_DTYPE),
+            None if accept_of is None else _records(accept_of, np.uint32))
+
+
+def socks_from_accept(conns, slots, listeners, ring_off, ring_size, mss: int = 1460):
+    """How the connections an accept call opened are listed for the next calls. `conns`: the
+    ACCEPT_CONN_DTYPE records of the call (host array), `slots` and `listeners` the lists it was given;
+    `ring_off` and `ring_size`: per slot (an array of n_slots entries, or one value for all) where the
+    connection's RX ring lies in `rings`. Returns (idx, socks, snd, tx) for the filled slots, in slot
+    order: idx their slot numbers; socks SOCK_DTYPE rows (key, rcv_nxt, rcv_wnd = the slot's, snd_nxt =
+    iss + 1, an empty ring); snd SND_DTYPE rows {iss, the SYN's window}: the handshake's third ACK is then
+    code 1 with snd_una == iss + 1; tx TX_SOCK_DTYPE rows whose 54-byte header template answers the peer
+    (addresses and ports swapped, the listener's MAC, the ID seed advanced past the SYN-ACK, mss = the
+    peer's or `mss` when the SYN had none, the send state snd_una = snd_nxt = iss + 1)."""
+    conns = np.atleast_1d(np.asarray(conns, dtype=ACCEPT_CONN_DTYPE))
+    slots = np.atleast_1d(np.asarray(slots, dtype=ACCEPT_SLOT_DTYPE))
+    listeners = np.atleast_1d(np.asarray(listeners, dtype=LISTENER_DTYPE))
+    assert conns.size == slots.size, "one connection record per slot"
+    idx = np.flatnonzero(conns["used"])
+    ring_off = np.broadcast_to(np.asarray(ring_off, dtype=np.uint64), (slots.size,))[idx]
+    ring_size = np.broadcast_to(np.asarray(ring_size, dtype=np.uint32), (slots.size,))[idx]
+    c, s = conns[idx], slots[idx]
+    # a slot's listener: the one whose range holds it
+    owner = np.full(slots.size, -1, dtype=np.int64)
+    for k, l in enumerate(listeners):
+        owner[int(l["slot_first"]) : int(l["slot_first"]) + int(l["n_slots"])] = k
+    assert (owner[idx] >= 0).all(), "a filled slot belongs to a listener"
+    lis = listeners[owner[idx]]
+    socks = np.zeros(idx.size, dtype=SOCK_DTYPE)
+    socks["key"], socks["rcv_nxt"], socks["rcv_wnd"], socks["snd_nxt"] = c["key"], c["rcv_nxt"], s["rcv_wnd"], c["snd_nxt"]
+    socks["ring_size"], socks["ring_off"], socks["ring_wpos"], socks["ring_free"] = ring_size, ring_off, 0, ring_size
+    snd = np.zeros(idx.size, dtype=SND_DTYPE)
+    snd["snd_una"], snd["snd_wnd"] = s["iss"], c["snd_wnd"]
+    tx = np.zeros(idx.size, dtype=TX_SOCK_DTYPE)
+    hdr = tx["hdr"]
+    hdr[:, 0:6], hdr[:, 6:12] = c["remote_mac"], lis["mac"]
+    hdr[:, 12], hdr[:, 14], hdr[:, 22], hdr[:, 23], hdr[:, 46] = 0x08, 0x45, 64, 6, 0x50
+    for k in range(idx.size):  # the ID the connection's next frame carries: two steps past the seed
+        nxt = _prand16(_prand16(int(s["ip_id"][k])))
+        hdr[k, 18], hdr[k, 19] = nxt >> 8, nxt & 0xFF
+    hdr[:, 26:30], hdr[:, 30:34] = c["key"][:, 5:9], c["key"][:, 1:5]
+    hdr[:, 34:36], hdr[:, 36:38] = c["key"][:, 11:13], c["key"][:, 9:11]
+    tx["mss"] = np.minimum(np.where(c["peer_mss"] != 0, c["peer_mss"], mss), 65495)  # (the ring send's largest chunk)
+    tx["snd_una"] = tx["snd_nxt"] = c["snd_nxt"]
+    tx["snd_wnd"], tx["rcv_nxt"], tx["rcv_wnd"] = c["snd_wnd"], c["rcv_nxt"], s["rcv_wnd"]
+    return idx, socks, snd, tx
+
+
+def _prand16(x: int) -> int:
+    """The reference's IPv4 ID generator (stacks/port_tcp.go:197-203)."""
+    x ^= (x << 7) & 0xFFFF
+    x ^= x >> 9
+    x ^= (x << 8) & 0xFFFF
+    return x
 
 
 def shard_count(n: int, nshards: int, shard: int) -> int:
