@@ -91,6 +91,17 @@ LISTENER_OUT_DTYPE = np.dtype([("n_syn", "<u4"), ("n_accepted", "<u4"), ("n_full
 ACCEPT_STRIDE = 64
 ACCEPT_NONE, ACCEPT_FULL = 0xFFFFFFFF, 0xFFFFFFFE  # accept_of of a flow that is no candidate / found no slot
 ACCEPT_MAX_LISTENERS = ACCEPT_MAX_SLOTS = 65536
+# The close call (include/framesum_close.h): fs_cl_sock (40 bytes) and fs_cl_out (32), neither with padding
+CLOSER_DTYPE = np.dtype([("key", "u1", (13,)), ("state", "u1"), ("reserved", "u1", (2,)), ("rcv_nxt", "<u4"),
+                         ("rcv_wnd", "<u4"), ("snd_una", "<u4"), ("snd_nxt", "<u4"), ("snd_wnd", "<u4"), ("reserved2", "<u4")])
+CLOSE_OUT_DTYPE = np.dtype([("state", "<u4"), ("rcv_nxt", "<u4"), ("snd_una", "<u4"), ("snd_wnd", "<u4"), ("n_taken", "<u4"),
+                            ("n_rejected", "<u4"), ("stop", "<u4"), ("flags", "<u4")])
+# the reference's state numbers (seqs.go:175-208)
+ST_CLOSED, ST_ESTABLISHED, ST_FIN_WAIT_1, ST_FIN_WAIT_2, ST_CLOSING, ST_TIME_WAIT, ST_CLOSE_WAIT, ST_LAST_ACK = 0, 4, 5, 6, 7, 8, 9, 10
+# the per-frame codes of the close call's ctl_code (1, 4 and 5 as the receive call's)
+CLOSE_NONE, CLOSE_TAKEN, CLOSE_REJECTED, CLOSE_KEEPALIVE, CLOSE_DATA, CLOSE_IGNORED, CLOSE_RST, CLOSE_EXPECTED = 0, 1, 4, 5, 7, 8, 9, 10
+CLOSE_ACK_OWED, CLOSE_FIN, CLOSE_RESET = 1, 2, 4  # fs_cl_out.flags
+CLOSE_MAX_CLOSERS = 65536
 # fs_tx_sock: one socket of the ring send (104 bytes, no padding), and fs_tx_sock_out (32 bytes)
 TX_SOCK_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("ring_off", "<u8"), ("ring_size", "<u4"),
                           ("ring_rpos", "<u4"), ("ring_buffered", "<u4"), ("snd_una", "<u4"), ("snd_nxt", "<u4"),
@@ -202,6 +213,20 @@ ACCEPT_PROTOTYPES = {
                                          _p, _u64, _p, _p, _p, _p, _p, _p, _p]),
 }
 
+# The functions include/framesum_close.h declares (the sixth header), in its order: product symbols too.
+# The accept call's prototypes with closers, n_closers, closers_out, socks_close and ctl_code behind
+# `synack_status`.
+CLOSE_PROTOTYPES = {
+    "fs_close_flows_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p,
+                                   _p, _u32, _p, _u32, _u32, _p, _p, _p, _p, _p, _p,
+                                   _p, _u32, _p, _p, _p,
+                                   _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "fs_close_flows_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p,
+                                        _p, _u32, _p, _u32, _u32, _p, _p, _p, _p, _p, _p,
+                                        _p, _u32, _p, _p, _p,
+                                        _p, _u64, _p, _p, _p, _p, _p, _p, _p]),
+}
+
 # Not in the header, set only where the loaded library has them: the test library's hooks
 # (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
 OPTIONAL_PROTOTYPES = {
@@ -238,7 +263,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         raise FramesumError(f"{p} is missing — run __graft_entry__.build() (or make -C seqs_amd/csrc)")
     lib = ctypes.CDLL(p)
     tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **RECV_PROTOTYPES, **ACCEPT_PROTOTYPES,
-              **OPTIONAL_PROTOTYPES}
+              **CLOSE_PROTOTYPES, **OPTIONAL_PROTOTYPES}
     for name, (restype, argtypes) in tables.items():
         if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
             continue

@@ -1,4 +1,4 @@
-// framesum C ABI -- the five RX call kinds, each with a device form and a host form:
+// framesum C ABI -- the six RX call kinds, each with a device form and a host form:
 //   the plain coalesce       fs_coalesce_batch, fs_coalesce_batch_host (include/framesum.h;
 //                            kernels: framesum_coalesce.hip)
 //   the flow-aware coalesce  fs_coalesce_flows_batch, ..._host (framesum_flows.hip)
@@ -9,6 +9,9 @@
 //   the accept call          fs_accept_flows_batch, ..._host (include/framesum_accept.h;
 //                            framesum_accept.hip): the receive call, then the passive open of every first
 //                            SYN to a listener, with its SYN-ACK
+//   the close call           fs_close_flows_batch, ..._host (include/framesum_close.h;
+//                            framesum_close.hip): the accept call, then the control walks of the closing
+//                            states and of an RST
 // A call is one record (RxCall) that the entry point fills from its flat arguments; the checks, the
 // stages up to the call's kind and the one host form all read that record.
 #include <algorithm>
@@ -17,6 +20,7 @@
 #include <vector>
 
 #include "framesum_accept.h"
+#include "framesum_close.h"
 #include "framesum_ctx.h"
 #include "framesum_deliver.h"
 #include "framesum_flows.h"
@@ -31,6 +35,7 @@ namespace rxp = framesum::plan::rx;
 namespace dl = framesum::deliver;
 namespace rv = framesum::recv;
 namespace ac = framesum::accept;
+namespace cl = framesum::closing;
 
 namespace {
 
@@ -40,6 +45,14 @@ struct RxListen {
     const fs_listener* listeners = nullptr;
     const fs_accept_slot* slots = nullptr;
     framesum::RxAccept x{};
+    std::vector<uint32_t> table;
+};
+
+// The closing part of a close call: the caller's list, where its own results go (y: the caller's
+// pointers, host or device as the form has them), and the closer table check_closers builds.
+struct RxClosing {
+    const fs_cl_sock* closers = nullptr;
+    framesum::RxClose y{};
     std::vector<uint32_t> table;
 };
 
@@ -61,6 +74,7 @@ struct RxCall {
     RxResults r{};
     RxSocks s;
     RxListen l;
+    RxClosing k;
     RxCall(rxp::Kind kind_, const char* fn_, const RxBatch& b_) : kind(kind_), fn(fn_), b(b_) {}
     // the flat arguments, group by group as the ABI lists them
     void coalesce(uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, void* totals, fs_digest* out,
@@ -84,6 +98,11 @@ struct RxCall {
         l.x = framesum::RxAccept{s.n_socks, n_listeners, n_slots, synack_flags, conns, listeners_out,
                                  accept_of,  synacks,     synack_out, synack_status};
     }
+    void closing(const fs_cl_sock* closers, uint32_t n_closers, fs_cl_out* closers_out, fs_cl_out* socks_close,
+                 uint8_t* ctl_code) {
+        k.closers = closers;
+        k.y = framesum::RxClose{s.n_socks, n_closers, closers_out, socks_close, ctl_code};
+    }
 };
 // The call as the launches see it: in the device forms the caller's batch and arrays on the caller's
 // stream, in the host forms the staged batch and the context's device arrays on the compute stream.
@@ -91,7 +110,8 @@ struct RxDevice {
     RxBatch b;
     RxResults r;
     hipStream_t stream;
-    framesum::RxAccept x{};  // (the accept call only)
+    framesum::RxAccept x{};  // (the accept call and the close call)
+    framesum::RxClose y{};   // (the close call only)
 };
 
 fs_status invalid(fs_ctx* ctx, const RxCall& c, const std::string& what) {
@@ -124,13 +144,21 @@ fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
         const rv::CheckSnd cs = rv::check_snd(c.s.socks, c.s.snd, c.s.n_socks, c.r.snd_out() != nullptr);
         if (cs.bad != rv::kSndGood) return invalid(ctx, c, "socket " + std::to_string(cs.sock) + ": " + rv::bad_snd_text(cs.bad));
     }
-    if (c.kind == rxp::kAccept) {  // the listener and slot lists' checks (framesum_accept.h), which also build the table
+    if (c.kind >= rxp::kAccept) {  // the listener and slot lists' checks (framesum_accept.h), which also build the table
         RxListen& l = c.l;
         const ac::CheckAccept ca =
             ac::check_accept(l.listeners, l.x.n_listeners, l.slots, l.x.n_slots, l.x.synack_flags, l.x.conns != nullptr,
                              l.x.listeners_out != nullptr, l.x.synacks != nullptr, ctx->flow_hash_mask, l.table);
         if (ca.bad != ac::kAcceptGood)
             return invalid(ctx, c, "listener or slot " + std::to_string(ca.index) + ": " + ac::bad_accept_text(ca.bad));
+    }
+    if (c.kind == rxp::kClose) {  // the closer list's checks (framesum_close.h), which also build the table
+        RxClosing& k = c.k;
+        const cl::CheckClose cc =
+            cl::check_closers(k.closers, k.y.n_closers, k.y.closers_out != nullptr, k.y.socks_close != nullptr, c.s.socks,
+                              c.s.n_socks, c.s.table.data(), ctx->flow_hash_mask, k.table);
+        if (cc.bad != cl::kCloseGood)
+            return invalid(ctx, c, "closer " + std::to_string(cc.index) + ": " + cl::bad_close_text(cc.bad));
     }
     return FS_SUCCESS;
 }
@@ -244,6 +272,25 @@ fs_status accept_stage(fs_ctx* ctx, const RxListen& l, const RxDevice& d, const 
     return staged_launch(ctx, blk.bytes, d.stream, "fs_accept_flows_batch: launch", fill, kernels);
 }
 
+// `ctl_code` zeroed; then, with a closer or a socket listed, the closers, their table and the sockets'
+// fixed values staged in a block of their own and the close kernels (which run for an empty batch too:
+// the out records are written).
+fs_status close_stage(fs_ctx* ctx, const RxCall& c, const RxDevice& d, const RxLaunch& how, RxLeft& left) {
+    const framesum::RxClose& y = d.y;
+    if (d.b.n != 0 && y.ctl_code) FS_HIP(ctx, hipMemsetAsync(y.ctl_code, 0, d.b.n, d.stream));
+    if (y.n_closers == 0 && y.n_socks == 0) return FS_SUCCESS;
+    left.cs = framesum::close_scratch(d.b.n, y.n_closers);
+    const fs_status st = ctx->cl_scratch.grow(ctx, left.cs.bytes);
+    if (st != FS_SUCCESS) return st;
+    left.close_scratch = ctx->cl_scratch.p;
+    const cl::Block blk = cl::block_of(y.n_closers, y.n_socks);
+    const auto fill = [&](uint8_t* h_block) {
+        cl::stage(c.k.closers, y.n_closers, c.k.table.data(), c.s.socks, y.n_socks, blk, h_block);
+    };
+    const auto kernels = [&](const uint8_t* d_block) { return framesum::launch_close(d.b, d.r, y, left, d_block, how); };
+    return staged_launch(ctx, blk.bytes, d.stream, "fs_close_flows_batch: launch", fill, kernels);
+}
+
 // The stages up to the call's kind. An empty batch has zero totals in place of its gather; the socket
 // calls still run their walks then. `left`: what the stages left (`copied`: non-empty batches only).
 fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
@@ -256,7 +303,8 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
         st = c.kind == rxp::kPlain ? plain_stage(ctx, d, how, left) : flows_stage(ctx, d, how, left);
     if (st == FS_SUCCESS && c.kind >= rxp::kDeliver) st = deliver_stage(ctx, c.s, d, how, left);
     if (st == FS_SUCCESS && c.kind >= rxp::kRecv) st = recv_stage(ctx, c.s, d, how, left);
-    if (st == FS_SUCCESS && c.kind == rxp::kAccept) st = accept_stage(ctx, c.l, d, how, left);
+    if (st == FS_SUCCESS && c.kind >= rxp::kAccept) st = accept_stage(ctx, c.l, d, how, left);
+    if (st == FS_SUCCESS && c.kind == rxp::kClose) st = close_stage(ctx, c, d, how, left);
     return st;
 }
 
@@ -264,7 +312,7 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
 fs_status rx_device(fs_ctx* ctx, const RxCall& c, void* stream) {
     FS_HIP(ctx, hipSetDevice(ctx->device));
     RxLeft left;
-    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.x}, left);
+    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.x, c.k.y}, left);
 }
 
 // A checked host form: the batch staged through slot 0, the result arrays carved from the context's
@@ -281,16 +329,24 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
         for (uint32_t i = 0; sockets && i < s.n_socks; ++i) h.socks_out()[i] = dl::untouched(s.socks[i]);
         for (uint32_t i = 0; c.kind >= rxp::kRecv && i < s.n_socks; ++i)
             h.snd_out()[i] = rv::untouched(s.snd[i].snd_una, s.snd[i].snd_wnd);
-        if (c.kind == rxp::kAccept) {  // no slot is filled, no listener has a candidate
+        if (c.kind >= rxp::kAccept) {  // no slot is filled, no listener has a candidate
             if (c.l.x.n_slots) std::memset(c.l.x.conns, 0, (uint64_t)c.l.x.n_slots * sizeof(fs_accept_conn));
             if (c.l.x.n_listeners) std::memset(c.l.x.listeners_out, 0, (uint64_t)c.l.x.n_listeners * sizeof(fs_listener_out));
+        }
+        if (c.kind == rxp::kClose) {  // no connection has a flow
+            for (uint32_t i = 0; i < c.k.y.n_closers; ++i) c.k.y.closers_out[i] = cl::untouched_closer(c.k.closers[i]);
+            for (uint32_t i = 0; i < s.n_socks; ++i)
+                c.k.y.socks_close[i] = cl::untouched_sock(s.socks[i].rcv_nxt, s.snd[i].snd_una, s.snd[i].snd_wnd, cl::kNone);
         }
         return FS_SUCCESS;
     }
     // the accept call's own arrays, as the caller passed them, in plan::rx::AcceptArray's order
-    const bool accepts = c.kind == rxp::kAccept;
+    const bool accepts = c.kind >= rxp::kAccept, closes = c.kind == rxp::kClose;
     const framesum::RxAccept& hx = c.l.x;
     void* const h_accept[rxp::kAcceptArrays] = {hx.conns, hx.listeners_out, hx.accept_of, hx.synacks, hx.synack_out, hx.synack_status};
+    // the close call's own arrays likewise, in plan::rx::CloseArray's order
+    const framesum::RxClose& hy = c.k.y;
+    void* const h_close[rxp::kCloseArrays] = {hy.closers_out, hy.socks_close, hy.ctl_code};
     const framesum::plan::Scan sc = framesum::plan::scan_batch(b.offsets, b.lengths, n, frames_bytes);
     if (sc.bad < n) return invalid(ctx, c, "frame " + std::to_string(sc.bad) + " ends past frames_bytes");
     // the device payload buffer: payload_cap, or the most payload the batch can hold when that is less
@@ -299,13 +355,14 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     const uint64_t span = s.span.hi - s.span.lo;
     const rxp::Layout L = rxp::layout(c.kind, n, s.n_socks);
     const rxp::AcceptLayout AL = rxp::accept_layout(L.bytes, n, hx.n_listeners, hx.n_slots);
+    const rxp::CloseLayout CL = rxp::close_layout(AL.bytes, n, s.n_socks, hy.n_closers);
     fs_status st = begin_host_call(ctx);
     if (st == FS_SUCCESS && sockets) st = ctx->dl_rings.grow(ctx, span);
     // (the socket calls begin once more, behind the rings' buffer: a second hipSetDevice that keeps their
     // sequence of HIP calls what profiles/rx_call_refactor/calls.txt compares)
     if (st == FS_SUCCESS && sockets) st = begin_host_call(ctx);
     if (st == FS_SUCCESS) st = ctx->co_payload.grow(ctx, d_cap);
-    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, accepts ? AL.bytes : L.bytes);
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, closes ? CL.bytes : accepts ? AL.bytes : L.bytes);
     if (st != FS_SUCCESS) return st;
     Staged sg;
     st = stage_batch(ctx, b.frames, frames_bytes, sc.lo, sc.hi, b.offsets, b.lengths, n, sg);
@@ -333,6 +390,11 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
                              static_cast<uint8_t*>(d_accept[rxp::kSynacks]),
                              static_cast<fs_digest*>(d_accept[rxp::kSynackOut]),
                              static_cast<uint8_t*>(d_accept[rxp::kSynackStatus])};
+    void* d_close[rxp::kCloseArrays] = {};
+    for (uint32_t a = 0; closes && a < rxp::kCloseArrays; ++a)
+        if (h_close[a] && CL.room[a] != 0) d_close[a] = ctx->rx_arrays.p + CL.at[a];
+    d.y = framesum::RxClose{hy.n_socks, hy.n_closers, static_cast<fs_cl_out*>(d_close[rxp::kClosersOut]),
+                            static_cast<fs_cl_out*>(d_close[rxp::kSocksClose]), static_cast<uint8_t*>(d_close[rxp::kCtlCode])};
     RxLeft left;
     st = rx_run(ctx, c, d, left);
     if (st != FS_SUCCESS) {
@@ -362,6 +424,8 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
         FS_HIP_DRAIN(ctx, back(h.array[a], d.r.array[a], rxp::bytes_back(c.kind, (rxp::Array)a, n, s.n_socks, got)));
     for (uint32_t a = 0; accepts && a < rxp::kAcceptArrays; ++a)
         FS_HIP_DRAIN(ctx, back(d_accept[a] ? h_accept[a] : nullptr, d_accept[a], AL.room[a]));
+    for (uint32_t a = 0; closes && a < rxp::kCloseArrays; ++a)
+        FS_HIP_DRAIN(ctx, back(d_close[a] ? h_close[a] : nullptr, d_close[a], CL.room[a]));
     FS_HIP_DRAIN(ctx, back(s.n_socks ? h.rings + s.span.lo : nullptr, ctx->dl_rings.p, span));
     FS_HIP_DRAIN(ctx, back(h.out, sg.d_out, (uint64_t)n * sizeof(fs_digest)));
     FS_HIP_DRAIN(ctx, back(h.status, sg.d_st, n));
@@ -372,7 +436,7 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
 
 }  // namespace
 
-// ---- The eight entry points: fill the record, check, run.
+// ---- The twelve entry points: fill the record, check, run.
 
 fs_status fs_coalesce_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
                             uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
@@ -534,6 +598,56 @@ fs_status fs_accept_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_
     c.send_side(snd, snd_out, code);
     c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
                 synack_status);
+    const fs_status st = rx_check(ctx, c, false);
+    return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
+}
+
+fs_status fs_close_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                               uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
+                               uint8_t* rings, uint64_t rings_bytes, fs_rx_sock_out* socks_out, uint8_t* delivered,
+                               const fs_rx_snd* snd, fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                               uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots, uint32_t synack_flags,
+                               fs_accept_conn* conns, fs_listener_out* listeners_out, uint32_t* accept_of,
+                               uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status, const fs_cl_sock* closers,
+                               uint32_t n_closers, fs_cl_out* closers_out, fs_cl_out* socks_close, uint8_t* ctl_code,
+                               uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order,
+                               uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kClose, "fs_close_flows_batch", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
+    c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
+    const fs_status st = rx_check(ctx, c, true);
+    return st != FS_SUCCESS ? st : rx_device(ctx, c, stream);
+}
+
+fs_status fs_close_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                                    const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags,
+                                    const fs_rx_sock* socks, uint32_t n_socks, uint8_t* rings, uint64_t rings_bytes,
+                                    fs_rx_sock_out* socks_out, uint8_t* delivered, const fs_rx_snd* snd,
+                                    fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                                    uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots,
+                                    uint32_t synack_flags, fs_accept_conn* conns, fs_listener_out* listeners_out,
+                                    uint32_t* accept_of, uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status,
+                                    const fs_cl_sock* closers, uint32_t n_closers, fs_cl_out* closers_out,
+                                    fs_cl_out* socks_close, uint8_t* ctl_code, uint8_t* payload, uint64_t payload_cap,
+                                    fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
+                                    fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kClose, "fs_close_flows_batch_host", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
+    c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
     const fs_status st = rx_check(ctx, c, false);
     return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
 }

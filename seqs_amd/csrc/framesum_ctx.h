@@ -1,6 +1,6 @@
 // Internal to the host side of the C ABI (framesum_api.cpp: context lifecycle, digest and fill calls;
-// framesum_api_tx.cpp: the TX frame build; framesum_api_rx.cpp: the five RX call kinds -- the plain and
-// the flow-aware coalesce, the delivery into socket rings, the receive call and the accept call): the context, the error
+// framesum_api_tx.cpp: the TX frame build; framesum_api_rx.cpp: the six RX call kinds -- the plain and
+// the flow-aware coalesce, the delivery into socket rings, the receive call, the accept call and the close call): the context, the error
 // helpers and macros, the grow-only device buffer, the staging blocks and the launch behind one, and the
 // staging helpers of the host-staged calls that stage one batch through slot 0. Defined in
 // framesum_api.cpp.
@@ -117,6 +117,9 @@ struct fs_ctx {
     // the accept call: the kernels' scratch; the listeners, their table and the slots are staged through
     // seg_stage like the delivery's block, and the SYN-ACK kernel reads d_seg_tables.
     DevBuf ac_scratch;
+    // the close call: the kernels' scratch; the closers, their table and the sockets' fixed values are
+    // staged through seg_stage like the delivery's block.
+    DevBuf cl_scratch;
     std::string err;
 };
 

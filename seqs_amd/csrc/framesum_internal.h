@@ -10,6 +10,7 @@
 #include "../../include/framesum_deliver.h"
 #include "../../include/framesum_recv.h"
 #include "../../include/framesum_accept.h"
+#include "../../include/framesum_close.h"
 #include "framesum_choice.h"
 #include "framesum_plan.h"
 
@@ -100,9 +101,10 @@ hipError_t launch_send_rings(const uint8_t* d_block, const segment::Block& b, ui
                              int workgroups, hipStream_t stream);
 
 // ---- The RX calls (framesum_coalesce.hip, framesum_flows.hip, framesum_deliver.hip, framesum_recv.hip,
-// framesum_accept.hip). A call is a row of stages on one stream -- the digest launch and the plain or the
-// flow-aware gather, then the delivery, then the receive call's fold, then the accept call's passive open
-// -- each behind the one before it and reading what it left. The launches take the call as a few records.
+// framesum_accept.hip, framesum_close.hip). A call is a row of stages on one stream -- the digest launch and
+// the plain or the flow-aware gather, then the delivery, then the receive call's fold, then the accept
+// call's passive open, then the close call's control walks -- each behind the one before it and reading
+// what it left. The launches take the call as a few records.
 
 // The batch as the launches read it.
 struct RxBatch {
@@ -167,11 +169,16 @@ struct RecvScratch {
 struct AcceptScratch {
     uint64_t rank_in, rank_sorted, synrec, cand_frame, sort_temp, sort_bytes, bytes;
 };
+// CloseScratch: 16-byte aligned; 20 bytes per frame and 4 per closer.
+struct CloseScratch {
+    uint64_t sq, flow_closer, closer_first, bytes;
+};
 CoScratch coalesce_scratch(uint32_t n);
 FlowScratch flows_scratch(uint32_t n);
 DeliverScratch deliver_scratch(uint32_t n, uint32_t n_socks);
 RecvScratch recv_scratch(uint32_t n);
 AcceptScratch accept_scratch(uint32_t n, uint32_t n_listeners, uint32_t n_slots);
+CloseScratch close_scratch(uint32_t n, uint32_t n_closers);
 
 // What the accept call has beside a receive call's batch and results: the counts of its staged lists and
 // where its own results go on the device (the caller's pointers in the device form, the context's device
@@ -184,6 +191,15 @@ struct RxAccept {
     uint8_t* synacks;
     fs_digest* synack_out;
     uint8_t* synack_status;
+};
+
+// What the close call has beside an accept call's: the counts of its lists and where its own results go
+// on the device (ctl_code is nullable).
+struct RxClose {
+    uint32_t n_socks, n_closers;
+    fs_cl_out* closers_out;
+    fs_cl_out* socks_close;
+    uint8_t* ctl_code;
 };
 
 // What the stages of one call leave on the device for the stages behind them: each stage's scratch, laid
@@ -199,6 +215,8 @@ struct RxLeft {
     RecvScratch rs;
     uint8_t* accept_scratch;
     AcceptScratch acs;
+    uint8_t* close_scratch;
+    CloseScratch cs;
 };
 
 // The launches that follow a batch's digest launch on the stream (fs_coalesce_batch in
@@ -228,5 +246,13 @@ hipError_t launch_recv(const RxBatch& b, const RxResults& r, const RxLeft& left,
 // "nothing" values by the caller.
 hipError_t launch_accept(const RxBatch& b, const RxAccept& x, const RxLeft& left, const uint8_t* d_block,
                          const SegTables* tables, int tx_workgroups, const RxLaunch& how);
+
+// The launches that follow a batch's accept launches (fs_close_flows_batch in include/framesum_close.h)
+// and read what the flow launches and, with sockets listed, the delivery and the receive launches left,
+// `r.socks_out()` and `r.snd_out()`. `d_block`: the device copy of the staged block (framesum_close.h
+// block_of: the closers, their table, the listed sockets' fixed values); at least one closer or one
+// socket. y.ctl_code is zeroed by the caller. With n of 0 only the out records are written.
+hipError_t launch_close(const RxBatch& b, const RxResults& r, const RxClose& y, const RxLeft& left, const uint8_t* d_block,
+                        const RxLaunch& how);
 
 }  // namespace framesum

@@ -217,16 +217,17 @@ inline void host_chunks(const uint64_t* offsets, const uint32_t* lengths, uint32
 }
 
 // ---------------------------------------------------------------------------------------
-// The device result arrays of the five RX host forms (fs_coalesce_batch_host,
+// The device result arrays of the six RX host forms (fs_coalesce_batch_host,
 // fs_coalesce_flows_batch_host, fs_deliver_flows_batch_host, fs_recv_flows_batch_host and, with the
-// arrays of its own in the second table below, fs_accept_flows_batch_host), described
+// arrays of their own in the second and the third table below, fs_accept_flows_batch_host and
+// fs_close_flows_batch_host), described
 // once: which arrays a call kind has, what each is sized by, where each lies in the context's one
 // buffer, and how much of each comes back given the totals the device reported. The host forms carve
 // the buffer and copy back by walking this description (framesum_api_rx.cpp).
 namespace rx {
 
 // A kind has the arrays of the kinds before it and its own.
-enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv, kAccept };
+enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv, kAccept, kClose };
 enum Array : uint32_t { kTotals, kRuns, kFlowRecs, kOrder, kRunOf, kDelivered, kSocksOut, kSndOut, kCode, kArrays };
 // What counts an array's entries: one record, the batch's frames, the call's sockets, or (for what
 // comes back only) one of the totals.
@@ -322,6 +323,38 @@ inline AcceptLayout accept_layout(uint64_t base, uint64_t n, uint64_t n_listener
         at = (at + d.align - 1) / d.align * d.align;
         L.at[a] = at;
         L.room[a] = d.elem * (d.count == kPerSlot ? n_slots : d.count == kPerListener ? n_listeners : n);
+        at += L.room[a];
+    }
+    L.bytes = at;
+    return L;
+}
+
+// The sixth kind's own arrays (fs_close_flows_batch_host: the kind has every array above, and these), in
+// a third table: each lies behind the accept call's arrays in the same buffer, none goes to the device
+// first, and every one comes back whole.
+enum CloseArray : uint32_t { kClosersOut, kSocksClose, kCtlCode, kCloseArrays };
+enum CloseCount : uint32_t { kPerCloser, kPerSockOfCall, kPerFrameOfCall };
+struct CloseArrayDesc {
+    uint32_t elem, align;  // bytes per entry, and the alignment the kernels' stores want
+    CloseCount count;
+};
+constexpr CloseArrayDesc kCloseArrayDesc[kCloseArrays] = {
+    {32, 4, kPerCloser},       // fs_cl_out, per closer
+    {32, 4, kPerSockOfCall},   // fs_cl_out, per listed socket
+    {1, 1, kPerFrameOfCall},   // ctl_code
+};
+struct CloseLayout {
+    uint64_t at[kCloseArrays], room[kCloseArrays], bytes;  // `bytes`: the arrays above and these
+};
+// `base`: accept_layout(...).bytes.
+inline CloseLayout close_layout(uint64_t base, uint64_t n, uint64_t n_socks, uint64_t n_closers) {
+    CloseLayout L;
+    uint64_t at = base;
+    for (uint32_t a = 0; a < kCloseArrays; ++a) {
+        const CloseArrayDesc& d = kCloseArrayDesc[a];
+        at = (at + d.align - 1) / d.align * d.align;
+        L.at[a] = at;
+        L.room[a] = d.elem * (d.count == kPerCloser ? n_closers : d.count == kPerSockOfCall ? n_socks : n);
         at += L.room[a];
     }
     L.bytes = at;

@@ -23,6 +23,9 @@ import numpy as np
 from .abi import (  # noqa: F401 (re-exported: this module is the binding's public face)
     ACCEPT_CONN_DTYPE, ACCEPT_FULL, ACCEPT_MAX_LISTENERS, ACCEPT_MAX_SLOTS, ACCEPT_NONE, ACCEPT_PROTOTYPES, ACCEPT_SLOT_DTYPE,
     ACCEPT_STRIDE, LISTENER_DTYPE, LISTENER_OUT_DTYPE,
+    CLOSE_ACK_OWED, CLOSE_DATA, CLOSE_EXPECTED, CLOSE_FIN, CLOSE_IGNORED, CLOSE_KEEPALIVE, CLOSE_MAX_CLOSERS, CLOSE_NONE,
+    CLOSE_OUT_DTYPE, CLOSE_PROTOTYPES, CLOSE_REJECTED, CLOSE_RESET, CLOSE_RST, CLOSE_TAKEN, CLOSER_DTYPE,
+    ST_CLOSED, ST_CLOSE_WAIT, ST_CLOSING, ST_ESTABLISHED, ST_FIN_WAIT_1, ST_FIN_WAIT_2, ST_LAST_ACK, ST_TIME_WAIT,
     DELIVER_MAX_SOCKS, DELIVER_PROTOTYPES, DIGEST_DTYPE, EXPORTED_SYMBOLS, FCS_APPEND, FILL_CSUM, FLOW_DTYPE,
     FLOW_TOTALS_DTYPE, FS_E_HIP, FS_E_INVALID, FS_E_NODEVICE, FS_E_NOMEM, FS_ERR_FCS, FS_SUCCESS, NO_FLOW, NO_RUN,
     PROTOTYPES, RECV_ACK_OWED, RECV_DUPLICATE, RECV_FIN, RECV_KEEPALIVE, RECV_NONE, RECV_PROTOTYPES, RECV_REJECTED,
@@ -86,6 +89,7 @@ _RX_FLOWS = ("fs_coalesce_flows_batch", FLOW_TOTALS_DTYPE,
 _RX_DELIVER = ("fs_deliver_flows_batch", *_RX_FLOWS[1:])
 _RX_RECV = ("fs_recv_flows_batch", *_RX_FLOWS[1:])  # (the delivery call with snd, snd_out and code behind delivered)
 _RX_ACCEPT = ("fs_accept_flows_batch", *_RX_FLOWS[1:])  # (the receive call with the listening arguments behind code)
+_RX_CLOSE = ("fs_close_flows_batch", *_RX_FLOWS[1:])  # (the accept call with the closing arguments behind synack_status)
 
 
 @dataclass
@@ -562,7 +566,7 @@ class Engine(_Handle):
     def accept_flows_device(self, frames, offsets, lengths, socks: np.ndarray, snd: np.ndarray, rings,
                             listeners: np.ndarray, slots: np.ndarray, mtu: int = 0, flags: int = 0, synack_flags: int = 0,
                             payload=None, delivered: bool = True, code: bool = True, accept_of: bool = True,
-                            synacks=None, synack_results: bool = True, stream=None):
+                            synacks=None, synack_results: bool = True, stream=None, _closing=None):
         """recv_flows_device plus the passive open of every flow without a listed socket whose first
         frame is a SYN to a listener (fs_accept_flows_batch): `listeners` is a LISTENER_DTYPE array on the
         host (local address and port in wire order, the SYN-ACKs' source MAC, the listener's range of
@@ -614,13 +618,21 @@ class Engine(_Handle):
                 ptr(marks), _array_ptr(snd), _tensor_ptr(snd_out), ptr(codes),
                 _array_ptr(listeners), n_listeners, _array_ptr(slots), n_slots, synack_flags, ptr(conns), ptr(listeners_out),
                 ptr(of), ptr(synacks), ptr(syn_out), ptr(syn_st))
-        return (conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
-                *self._rx_device(_RX_ACCEPT, frames, offsets, lengths, mtu, flags, payload, stream, args))
+        rx, mine = _RX_ACCEPT, ()
+        if _closing is not None:  # close_flows_device: the closing arguments behind synack_status, its tensors in front
+            closers, ctl = _closing
+            closers_out = torch.empty((int(closers.size), CLOSE_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            socks_close = torch.empty((int(socks.size), CLOSE_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            ctl_code = torch.empty((n,), dtype=torch.uint8, device=dev) if ctl else None
+            args += (_array_ptr(closers), int(closers.size), ptr(closers_out), ptr(socks_close), ptr(ctl_code))
+            rx, mine = _RX_CLOSE, (closers_out, socks_close, ctl_code)
+        return (*mine, conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
+                *self._rx_device(rx, frames, offsets, lengths, mtu, flags, payload, stream, args))
 
     def accept_flows_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, socks: np.ndarray,
                           snd: np.ndarray, rings: np.ndarray, listeners: np.ndarray, slots: np.ndarray, mtu: int = 0,
                           flags: int = 0, synack_flags: int = 0, payload=None, delivered: bool = True, code: bool = True,
-                          accept_of: bool = True, synacks=None, synack_results: bool = True):
+                          accept_of: bool = True, synacks=None, synack_results: bool = True, _closing=None):
         """accept_flows_device from and to host memory (fs_accept_flows_batch_host). `synacks`: a
         writable uint8 array of n_slots * ACCEPT_STRIDE bytes (else a new zeroed one), written in place in
         the frame bytes of filled slots only. Returns (conns ACCEPT_CONN_DTYPE[n_slots], listeners_out
@@ -662,8 +674,45 @@ class Engine(_Handle):
                 ptr(marks), _array_ptr(snd), _array_ptr(snd_out), ptr(codes),
                 _array_ptr(listeners), n_listeners, _array_ptr(slots), n_slots, synack_flags, ptr(conns), ptr(listeners_out),
                 ptr(of), ptr(synacks), ptr(syn_out), ptr(syn_st))
-        return (conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
-                *self._rx_host(_RX_ACCEPT, frames, offsets, lengths, mtu, flags, payload, args))
+        rx, mine = _RX_ACCEPT, ()
+        if _closing is not None:  # close_flows_host
+            closers, ctl = _closing
+            closers_out = np.zeros(int(closers.size), dtype=CLOSE_OUT_DTYPE)
+            socks_close = np.zeros(int(socks.size), dtype=CLOSE_OUT_DTYPE)
+            ctl_code = np.zeros(n, dtype=np.uint8) if ctl else None
+            args += (_array_ptr(closers), int(closers.size), ptr(closers_out), ptr(socks_close), ptr(ctl_code))
+            rx, mine = _RX_CLOSE, (closers_out, socks_close, ctl_code)
+        return (*mine, conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
+                *self._rx_host(rx, frames, offsets, lengths, mtu, flags, payload, args))
+
+    # ---- the close call: the accept call plus the closing states and the RST (include/framesum_close.h) ----
+    def close_flows_device(self, frames, offsets, lengths, socks: np.ndarray, snd: np.ndarray, rings,
+                           listeners: np.ndarray, slots: np.ndarray, closers: np.ndarray, ctl_code: bool = True, **kw):
+        """accept_flows_device plus the receive side of the closing states and of an RST
+        (fs_close_flows_batch): `closers` is a CLOSER_DTYPE array on the host, the sockets whose
+        ControlBlock is in ST_FIN_WAIT_1 .. ST_LAST_ACK (key, state, rcv_nxt, rcv_wnd, snd_una, snd_nxt,
+        snd_wnd; a closer has no ring). Every closer's flow is walked under the rule of the header, and
+        every socket of `socks` goes on from where the receive call's walk ended at an admitted FIN or
+        at an RST. Further keyword arguments are accept_flows_device's. Returns (closers_out,
+        socks_close, ctl_code, then accept_flows_device's tuple) device tensors: closers_out (n_closers,
+        32) and socks_close (n_socks, 32) uint8 = CLOSE_OUT_DTYPE records (the state, rcv.NXT, snd.UNA and
+        snd.WND behind the walk, the counts, the walk's stop, CLOSE_ACK_OWED | CLOSE_FIN | CLOSE_RESET),
+        ctl_code (n,) uint8 (CLOSE_TAKEN .. CLOSE_EXPECTED for the frames a control walk handled,
+        CLOSE_NONE otherwise; None when `ctl_code` is False). Asynchronous on `stream`; split_close()
+        brings the records to the host."""
+        closers = np.ascontiguousarray(closers, dtype=CLOSER_DTYPE)
+        return self.accept_flows_device(frames, offsets, lengths, socks, snd, rings, listeners, slots,
+                                        _closing=(closers, ctl_code), **kw)
+
+    def close_flows_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, socks: np.ndarray,
+                         snd: np.ndarray, rings: np.ndarray, listeners: np.ndarray, slots: np.ndarray,
+                         closers: np.ndarray, ctl_code: bool = True, **kw):
+        """close_flows_device from and to host memory (fs_close_flows_batch_host). Returns (closers_out
+        CLOSE_OUT_DTYPE[n_closers], socks_close CLOSE_OUT_DTYPE[n_socks], ctl_code uint8[n] or None, then
+        accept_flows_host's tuple)."""
+        closers = np.ascontiguousarray(closers, dtype=CLOSER_DTYPE)
+        return self.accept_flows_host(frames, offsets, lengths, socks, snd, rings, listeners, slots,
+                                      _closing=(closers, ctl_code), **kw)
 
     # ---- TCP segments from socket TX rings (include/framesum_send.h) ------------
     @staticmethod
@@ -920,6 +969,45 @@ def split_accept(conns, listeners_out, accept_of=None):
     for them): (ACCEPT_CONN_DTYPE[n_slots], LISTENER_OUT_DTYPE[n_listeners], uint32[n] or None)."""
     return (_records(conns, ACCEPT_CONN_DTYPE), _records(listeners_out, LISTENER_OUT_DTYPE),
             None if accept_of is None else _records(accept_of, np.uint32))
+
+
+def split_close(closers_out, socks_close, ctl_code=None):
+    """The host view of close_flows_device's `closers_out`, `socks_close` and `ctl_code` tensors (this waits
+    for them): (CLOSE_OUT_DTYPE[n_closers], CLOSE_OUT_DTYPE[n_socks], uint8[n] or None)."""
+    return (_records(closers_out, CLOSE_OUT_DTYPE), _records(socks_close, CLOSE_OUT_DTYPE),
+            None if ctl_code is None else _records(ctl_code, np.uint8))
+
+
+def closers_from(socks, socks_close) -> tuple:
+    """How the sockets that left Established in a close call are listed for the next calls. `socks`: the
+    SOCK_DTYPE rows the call was given, `socks_close` its CLOSE_OUT_DTYPE records for them (host array).
+    Returns (idx, closers): idx the rows whose state is no longer ST_ESTABLISHED, closers their
+    CLOSER_DTYPE records (key, rcv_wnd and snd_nxt from the row; state, rcv_nxt, snd_una and snd_wnd from
+    the record). A row that came back ST_CLOSED or ST_TIME_WAIT is in idx too: the host drops it, or lists
+    it as a closer whose frames are then ignored."""
+    socks = np.atleast_1d(np.asarray(socks, dtype=SOCK_DTYPE))
+    out = np.atleast_1d(np.asarray(socks_close, dtype=CLOSE_OUT_DTYPE))
+    assert socks.size == out.size, "one close record per socket"
+    idx = np.flatnonzero(out["state"] != ST_ESTABLISHED)
+    closers = np.zeros(idx.size, dtype=CLOSER_DTYPE)
+    closers["key"], closers["rcv_wnd"], closers["snd_nxt"] = socks["key"][idx], socks["rcv_wnd"][idx], socks["snd_nxt"][idx]
+    for name in ("state", "rcv_nxt", "snd_una", "snd_wnd"):
+        closers[name] = out[name][idx]
+    return idx, closers
+
+
+def state_after_send(state: int, sent: int) -> int:
+    """Send's state changes (control_user.go:118-137) for a connection in `state` (the reference's number)
+    after a ring send whose fs_tx_sock_out.sent is `sent`: ST_ESTABLISHED + TX_FIN -> ST_FIN_WAIT_1,
+    ST_CLOSE_WAIT + TX_FIN -> ST_LAST_ACK, ST_CLOSING + TX_ACK -> ST_TIME_WAIT; every other pair keeps the
+    state."""
+    if sent & TX_FIN and state == ST_ESTABLISHED:
+        return ST_FIN_WAIT_1
+    if sent & TX_FIN and state == ST_CLOSE_WAIT:
+        return ST_LAST_ACK
+    if sent & TX_ACK and state == ST_CLOSING:
+        return ST_TIME_WAIT
+    return state
 
 
 def socks_from_accept(conns, slots, listeners, ring_off, ring_size, mss: int = 1460):
