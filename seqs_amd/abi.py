@@ -102,6 +102,18 @@ ST_CLOSED, ST_ESTABLISHED, ST_FIN_WAIT_1, ST_FIN_WAIT_2, ST_CLOSING, ST_TIME_WAI
 CLOSE_NONE, CLOSE_TAKEN, CLOSE_REJECTED, CLOSE_KEEPALIVE, CLOSE_DATA, CLOSE_IGNORED, CLOSE_RST, CLOSE_EXPECTED = 0, 1, 4, 5, 7, 8, 9, 10
 CLOSE_ACK_OWED, CLOSE_FIN, CLOSE_RESET = 1, 2, 4  # fs_cl_out.flags
 CLOSE_MAX_CLOSERS = 65536
+# The connect call (include/framesum_connect.h): fs_cn_sock (40 bytes) and fs_cn_out (48), neither with padding
+OPENER_DTYPE = np.dtype([("key", "u1", (13,)), ("flags", "u1"), ("reserved", "u1", (2,)), ("local_mac", "u1", (6,)),
+                         ("remote_mac", "u1", (6,)), ("iss", "<u4"), ("rcv_wnd", "<u4"), ("ip_id", "<u2"), ("reserved2", "<u2")])
+CONNECT_OUT_DTYPE = np.dtype([("state", "<u4"), ("irs", "<u4"), ("rcv_nxt", "<u4"), ("snd_una", "<u4"), ("snd_nxt", "<u4"),
+                              ("snd_wnd", "<u4"), ("n_rejected", "<u4"), ("n_keepalive", "<u4"), ("stop", "<u4"),
+                              ("frame", "<u4"), ("peer_mss", "<u2"), ("reply", "u1"), ("flags", "u1"), ("rst_seq", "<u4")])
+ST_LISTEN, ST_SYN_RCVD, ST_SYN_SENT = 1, 2, 3  # the reference's state numbers before Established
+CN_BAD_ACK = 11  # the connect call's own ctl_code value (1, 4, 5 and 10 keep their close-call names)
+CN_SEND_SYN = 1  # fs_cn_sock.flags
+CN_REPLY_NONE, CN_REPLY_ACK, CN_REPLY_SYNACK, CN_REPLY_RST, CN_REPLY_SYN = range(5)  # fs_cn_out.reply
+CN_STOP_RST, CN_STOP_SYN = 1, 2  # fs_cn_out.flags
+CONNECT_MAX_OPENERS = 65536
 # fs_tx_sock: one socket of the ring send (104 bytes, no padding), and fs_tx_sock_out (32 bytes)
 TX_SOCK_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("ring_off", "<u8"), ("ring_size", "<u4"),
                           ("ring_rpos", "<u4"), ("ring_buffered", "<u4"), ("snd_una", "<u4"), ("snd_nxt", "<u4"),
@@ -227,6 +239,22 @@ CLOSE_PROTOTYPES = {
                                         _p, _u64, _p, _p, _p, _p, _p, _p, _p]),
 }
 
+# The functions include/framesum_connect.h declares (the seventh header), in its order: product symbols too.
+# The close call's prototypes with openers, n_openers, reply_flags, openers_out, replies, reply_out and
+# reply_status behind `ctl_code`.
+CONNECT_PROTOTYPES = {
+    "fs_connect_flows_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p,
+                                     _p, _u32, _p, _u32, _u32, _p, _p, _p, _p, _p, _p,
+                                     _p, _u32, _p, _p, _p,
+                                     _p, _u32, _u32, _p, _p, _p, _p,
+                                     _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "fs_connect_flows_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p,
+                                          _p, _u32, _p, _u32, _u32, _p, _p, _p, _p, _p, _p,
+                                          _p, _u32, _p, _p, _p,
+                                          _p, _u32, _u32, _p, _p, _p, _p,
+                                          _p, _u64, _p, _p, _p, _p, _p, _p, _p]),
+}
+
 # Not in the header, set only where the loaded library has them: the test library's hooks
 # (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
 OPTIONAL_PROTOTYPES = {
@@ -263,7 +291,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         raise FramesumError(f"{p} is missing — run __graft_entry__.build() (or make -C seqs_amd/csrc)")
     lib = ctypes.CDLL(p)
     tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **RECV_PROTOTYPES, **ACCEPT_PROTOTYPES,
-              **CLOSE_PROTOTYPES, **OPTIONAL_PROTOTYPES}
+              **CLOSE_PROTOTYPES, **CONNECT_PROTOTYPES, **OPTIONAL_PROTOTYPES}
     for name, (restype, argtypes) in tables.items():
         if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
             continue

@@ -17,8 +17,9 @@
 //             32 steps) gives the candidate's rank r with no atomic; r < n_slots fills slots[slot_first
 //             + r] (the connection record, the SYN-ACK's record for the frame body), else FULL; the
 //             listener's last candidate writes the listener's counts.
-//   synack    one wave per slot, the TX frame build's body (framesum_tx_dev.h) over a piece source without
-//             payload: the 54 header bytes, both checksums, the FCS, the digest and the verdict.
+//   synack    one wave per slot, the control-frame body (framesum_ctlframe_dev.h: the TX frame build's body
+//             over a piece source without payload): the 54 header bytes, both checksums, the FCS, the
+//             digest and the verdict.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -27,6 +28,7 @@
 #include "framesum_accept.h"
 #include "framesum_coalesce.h"
 #include "framesum_coalesce_dev.h"
+#include "framesum_ctlframe_dev.h"
 #include "framesum_flows.h"
 #include "framesum_internal.h"
 #include "framesum_segment.h"
@@ -123,47 +125,15 @@ __global__ void __launch_bounds__(kThreads) accept_assign(const AcArgs a) {
         a.conns[slot] = c;
         segment::SendRec rec;
         ac::synack_template(lis, sl, c, rec.hdr);
-        rec.mss = 0;
-        rec.payload_off = 0;
-        rec.payload_len = 0;
-        rec.frames = 1;
-        rec.frame_base = (uint64_t)slot * ac::kStride;
-        rec.id_at = 0;
-        rec.pad = 0;
+        ctlframe::finish_rec(rec, slot);
         a.synrec[slot] = rec;
         if (a.accept_of) a.accept_of[f] = slot;
     }
 }
 
-// ---- The SYN-ACKs: the TX frame build's body over a record without payload (mss 0: one frame of all
-// its bytes, of which there are none).
-using SynArgs = txdev::Args<segment::SendRec>;
-struct NoPayload {
-    using Rec = segment::SendRec;
-    static constexpr bool kMayUdp = false, kMssZero = true;
-    static __device__ __forceinline__ uint32_t total(const Rec*) { return 0u; }
-    __device__ __forceinline__ NoPayload(const SynArgs&, const Rec*, uint32_t, uint32_t) {}
-    __device__ __forceinline__ void load(int, uint32_t d[4]) const { d[0] = d[1] = d[2] = d[3] = 0u; }
-};
-
-static_assert(!NoPayload::kMayUdp, "a SYN-ACK is TCP: the kernel has no protocol branch");
-
-__global__ void __launch_bounds__(txdev::kThreads) accept_synack(const SynArgs a, const fs_accept_conn* conns) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // a workgroup none of whose slots was filled builds no tables (a batch without a SYN: all of them)
-    int mine = 0;
-    for (uint32_t slot = blockIdx.x * txdev::kWaves + wave; slot < a.n_frames; slot += gridDim.x * txdev::kWaves)
-        mine |= conns[slot].used;
-    if (!__syncthreads_or(mine)) return;
-    txdev::load_tables(a.tables);
-    // (a.n_frames: the slots; a filled slot's frame is the slot's)
-    for (uint32_t slot = blockIdx.x * txdev::kWaves + wave; slot < a.n_frames; slot += gridDim.x * txdev::kWaves) {
-        if (__builtin_amdgcn_readfirstlane((uint32_t)conns[slot].used) == 0u) continue;
-        const segment::SendRec* rec = a.recs + slot;
-        const uint32_t seed = __builtin_amdgcn_readfirstlane(((uint32_t)rec->hdr[18] << 8) | rec->hdr[19]);
-        txdev::build_frame<false, NoPayload>(a, rec, 0u, txdev::prand16(seed), slot, lane);
-    }
+// ---- The SYN-ACKs: the control-frame body (framesum_ctlframe_dev.h) over the filled slots.
+__global__ void __launch_bounds__(txdev::kThreads) accept_synack(const ctlframe::Args a, const fs_accept_conn* conns) {
+    ctlframe::build(a, reinterpret_cast<const uint8_t*>(conns) + offsetof(fs_accept_conn, used), sizeof(fs_accept_conn));
 }
 
 hipError_t sort_keys(void* temp, size_t& temp_bytes, uint64_t* in, uint64_t* out, uint32_t n, uint32_t bits,
@@ -233,26 +203,10 @@ hipError_t launch_accept(const RxBatch& b, const RxAccept& x, const RxLeft& left
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(accept_assign, dim3(scan_grid), dim3(kThreads), 0, stream, a);
     if (x.n_slots != 0) {
-        SynArgs sa;
-        sa.recs = a.synrec;
-        sa.prefix = nullptr;
-        sa.ids = nullptr;
-        sa.src = nullptr;
-        sa.frames = x.synacks;
-        sa.offsets = nullptr;
-        sa.lengths = nullptr;
-        sa.out = reinterpret_cast<uint2*>(x.synack_out);
-        sa.status = x.synack_status;
-        sa.tables = tables;
-        sa.n_recs = x.n_slots;
-        sa.n_frames = x.n_slots;
-        sa.tile = 1;
-        sa.mtu = b.mtu;
-        sa.flags = x.synack_flags;
-        sa.align = 1;
-        const uint32_t want = (x.n_slots + txdev::kWaves - 1u) / txdev::kWaves;
-        const uint32_t tx_cap = (uint32_t)(tx_workgroups > 0 ? tx_workgroups : 1);
-        hipLaunchKernelGGL(accept_synack, dim3(want < tx_cap ? want : tx_cap), dim3(txdev::kThreads), 0, stream, sa, x.conns);
+        const ctlframe::Args sa = ctlframe::args_of(a.synrec, x.n_slots, x.synacks, x.synack_out, x.synack_status, tables,
+                                                    b.mtu, x.synack_flags);
+        hipLaunchKernelGGL(accept_synack, dim3(ctlframe::grid_of(x.n_slots, tx_workgroups)), dim3(txdev::kThreads), 0, stream,
+                           sa, x.conns);
     }
     return hipGetLastError();
 }

@@ -1,4 +1,4 @@
-// framesum C ABI -- the six RX call kinds, each with a device form and a host form:
+// framesum C ABI -- the seven RX call kinds, each with a device form and a host form:
 //   the plain coalesce       fs_coalesce_batch, fs_coalesce_batch_host (include/framesum.h;
 //                            kernels: framesum_coalesce.hip)
 //   the flow-aware coalesce  fs_coalesce_flows_batch, ..._host (framesum_flows.hip)
@@ -12,6 +12,9 @@
 //   the close call           fs_close_flows_batch, ..._host (include/framesum_close.h;
 //                            framesum_close.hip): the accept call, then the control walks of the closing
 //                            states and of an RST
+//   the connect call         fs_connect_flows_batch, ..._host (include/framesum_connect.h;
+//                            framesum_connect.hip): the close call, then the active open of every listed
+//                            opener, with the control frame it owes
 // A call is one record (RxCall) that the entry point fills from its flat arguments; the checks, the
 // stages up to the call's kind and the one host form all read that record.
 #include <algorithm>
@@ -21,6 +24,7 @@
 
 #include "framesum_accept.h"
 #include "framesum_close.h"
+#include "framesum_connect.h"
 #include "framesum_ctx.h"
 #include "framesum_deliver.h"
 #include "framesum_flows.h"
@@ -36,6 +40,7 @@ namespace dl = framesum::deliver;
 namespace rv = framesum::recv;
 namespace ac = framesum::accept;
 namespace cl = framesum::closing;
+namespace cn = framesum::connect;
 
 namespace {
 
@@ -53,6 +58,14 @@ struct RxListen {
 struct RxClosing {
     const fs_cl_sock* closers = nullptr;
     framesum::RxClose y{};
+    std::vector<uint32_t> table;
+};
+
+// The opening part of a connect call: the caller's list, where its own results go (z: the caller's
+// pointers, host or device as the form has them), and the opener table check_openers builds.
+struct RxOpening {
+    const fs_cn_sock* openers = nullptr;
+    framesum::RxConnect z{};
     std::vector<uint32_t> table;
 };
 
@@ -75,6 +88,7 @@ struct RxCall {
     RxSocks s;
     RxListen l;
     RxClosing k;
+    RxOpening o;
     RxCall(rxp::Kind kind_, const char* fn_, const RxBatch& b_) : kind(kind_), fn(fn_), b(b_) {}
     // the flat arguments, group by group as the ABI lists them
     void coalesce(uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, void* totals, fs_digest* out,
@@ -103,6 +117,11 @@ struct RxCall {
         k.closers = closers;
         k.y = framesum::RxClose{s.n_socks, n_closers, closers_out, socks_close, ctl_code};
     }
+    void opening(const fs_cn_sock* openers, uint32_t n_openers, uint32_t reply_flags, fs_cn_out* openers_out, uint8_t* replies,
+                 fs_digest* reply_out, uint8_t* reply_status) {
+        o.openers = openers;
+        o.z = framesum::RxConnect{n_openers, reply_flags, openers_out, replies, reply_out, reply_status, k.y.ctl_code};
+    }
 };
 // The call as the launches see it: in the device forms the caller's batch and arrays on the caller's
 // stream, in the host forms the staged batch and the context's device arrays on the compute stream.
@@ -111,7 +130,8 @@ struct RxDevice {
     RxResults r;
     hipStream_t stream;
     framesum::RxAccept x{};  // (the accept call and the close call)
-    framesum::RxClose y{};   // (the close call only)
+    framesum::RxClose y{};   // (the close call and the connect call)
+    framesum::RxConnect z{}; // (the connect call only)
 };
 
 fs_status invalid(fs_ctx* ctx, const RxCall& c, const std::string& what) {
@@ -152,13 +172,22 @@ fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
         if (ca.bad != ac::kAcceptGood)
             return invalid(ctx, c, "listener or slot " + std::to_string(ca.index) + ": " + ac::bad_accept_text(ca.bad));
     }
-    if (c.kind == rxp::kClose) {  // the closer list's checks (framesum_close.h), which also build the table
+    if (c.kind >= rxp::kClose) {  // the closer list's checks (framesum_close.h), which also build the table
         RxClosing& k = c.k;
         const cl::CheckClose cc =
             cl::check_closers(k.closers, k.y.n_closers, k.y.closers_out != nullptr, k.y.socks_close != nullptr, c.s.socks,
                               c.s.n_socks, c.s.table.data(), ctx->flow_hash_mask, k.table);
         if (cc.bad != cl::kCloseGood)
             return invalid(ctx, c, "closer " + std::to_string(cc.index) + ": " + cl::bad_close_text(cc.bad));
+    }
+    if (c.kind == rxp::kConnect) {  // the opener list's checks (framesum_connect.h), which also build the table
+        RxOpening& o = c.o;
+        const cn::CheckConnect co =
+            cn::check_openers(o.openers, o.z.n_openers, o.z.reply_flags, o.z.openers_out != nullptr, o.z.replies != nullptr,
+                              c.s.socks, c.s.n_socks, c.s.table.data(), c.k.closers, c.k.y.n_closers, c.k.table.data(),
+                              ctx->flow_hash_mask, o.table);
+        if (co.bad != cn::kConnectGood)
+            return invalid(ctx, c, "opener " + std::to_string(co.index) + ": " + cn::bad_connect_text(co.bad));
     }
     return FS_SUCCESS;
 }
@@ -291,6 +320,26 @@ fs_status close_stage(fs_ctx* ctx, const RxCall& c, const RxDevice& d, const RxL
     return staged_launch(ctx, blk.bytes, d.stream, "fs_close_flows_batch: launch", fill, kernels);
 }
 
+// With an opener listed: the openers and their table staged in a block of their own and the connect
+// kernels (which run for an empty batch too: the out records and the flagged SYNs are written).
+fs_status connect_stage(fs_ctx* ctx, const RxCall& c, const RxDevice& d, const RxLaunch& how, RxLeft& left) {
+    const framesum::RxConnect& z = d.z;
+    if (z.n_openers == 0) return FS_SUCCESS;
+    left.cns = framesum::connect_scratch(d.b.n, z.n_openers);
+    fs_status st = ctx->cn_scratch.grow(ctx, left.cns.bytes);
+    if (st == FS_SUCCESS) st = seg_tables(ctx);
+    if (st != FS_SUCCESS) return st;
+    left.connect_scratch = ctx->cn_scratch.p;
+    // the reply kernel's grid as the TX frame build caps it (accept_stage)
+    const int tx_wgs = ctx->workgroups > 0 && ctx->workgroups < 2 * ctx->num_cus ? ctx->workgroups : 2 * ctx->num_cus;
+    const cn::Block blk = cn::block_of(z.n_openers);
+    const auto fill = [&](uint8_t* h_block) { cn::stage(c.o.openers, z.n_openers, c.o.table.data(), blk, h_block); };
+    const auto kernels = [&](const uint8_t* d_block) {
+        return framesum::launch_connect(d.b, d.r, z, left, d_block, ctx->d_seg_tables, tx_wgs, how);
+    };
+    return staged_launch(ctx, blk.bytes, d.stream, "fs_connect_flows_batch: launch", fill, kernels);
+}
+
 // The stages up to the call's kind. An empty batch has zero totals in place of its gather; the socket
 // calls still run their walks then. `left`: what the stages left (`copied`: non-empty batches only).
 fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
@@ -304,7 +353,8 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
     if (st == FS_SUCCESS && c.kind >= rxp::kDeliver) st = deliver_stage(ctx, c.s, d, how, left);
     if (st == FS_SUCCESS && c.kind >= rxp::kRecv) st = recv_stage(ctx, c.s, d, how, left);
     if (st == FS_SUCCESS && c.kind >= rxp::kAccept) st = accept_stage(ctx, c.l, d, how, left);
-    if (st == FS_SUCCESS && c.kind == rxp::kClose) st = close_stage(ctx, c, d, how, left);
+    if (st == FS_SUCCESS && c.kind >= rxp::kClose) st = close_stage(ctx, c, d, how, left);
+    if (st == FS_SUCCESS && c.kind == rxp::kConnect) st = connect_stage(ctx, c, d, how, left);
     return st;
 }
 
@@ -312,7 +362,49 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
 fs_status rx_device(fs_ctx* ctx, const RxCall& c, void* stream) {
     FS_HIP(ctx, hipSetDevice(ctx->device));
     RxLeft left;
-    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.x, c.k.y}, left);
+    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.x, c.k.y, c.o.z}, left);
+}
+
+// The connect part of a host form as the launches see it: `d_connect` holds the device arrays in
+// plan::rx::ConnectArray's order (null: the caller passed none).
+framesum::RxConnect connect_device(const framesum::RxConnect& hz, void* const d_connect[rxp::kConnectArrays], uint8_t* ctl_code) {
+    return framesum::RxConnect{hz.n_openers, hz.reply_flags, static_cast<fs_cn_out*>(d_connect[rxp::kOpenersOut]),
+                               static_cast<uint8_t*>(d_connect[rxp::kReplies]), static_cast<fs_digest*>(d_connect[rxp::kReplyOut]),
+                               static_cast<uint8_t*>(d_connect[rxp::kReplyStatus]), ctl_code};
+}
+
+// The connect call's host form without a batch: nothing is staged but the openers; the connect stage alone
+// runs on the compute stream over the context's device arrays, and its arrays come back.
+fs_status connect_host_empty(fs_ctx* ctx, const RxCall& c) {
+    const framesum::RxConnect& hz = c.o.z;
+    void* const h_connect[rxp::kConnectArrays] = {hz.openers_out, hz.replies, hz.reply_out, hz.reply_status};
+    const rxp::ConnectLayout NL = rxp::connect_layout(0, hz.n_openers);
+    fs_status st = begin_host_call(ctx);
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, NL.bytes);
+    if (st != FS_SUCCESS) return st;
+    const hipStream_t ks = ctx->compute_stream;
+    ctx->host_dirty = true;
+    void* d_connect[rxp::kConnectArrays] = {};
+    for (uint32_t a = 0; a < rxp::kConnectArrays; ++a) {
+        if (!h_connect[a] || NL.room[a] == 0) continue;
+        d_connect[a] = ctx->rx_arrays.p + NL.at[a];
+        if (rxp::kConnectArrayDesc[a].goes_in)
+            FS_HIP_DRAIN(ctx, hipMemcpyAsync(d_connect[a], h_connect[a], NL.room[a], hipMemcpyHostToDevice, ks));
+    }
+    RxDevice d{c.b, RxResults{}, ks};
+    d.z = connect_device(hz, d_connect, nullptr);
+    const RxLaunch how{rx_workgroups(ctx), ctx->flow_hash_mask, ctx->flow_steps, ks};
+    RxLeft left{};
+    st = connect_stage(ctx, c, d, how, left);
+    if (st != FS_SUCCESS) {
+        drain_host_streams(ctx);
+        return st;
+    }
+    for (uint32_t a = 0; a < rxp::kConnectArrays; ++a)
+        if (d_connect[a]) FS_HIP_DRAIN(ctx, hipMemcpyAsync(h_connect[a], d_connect[a], NL.room[a], hipMemcpyDeviceToHost, ks));
+    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
+    ctx->host_dirty = false;
+    return FS_SUCCESS;
 }
 
 // A checked host form: the batch staged through slot 0, the result arrays carved from the context's
@@ -333,20 +425,25 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
             if (c.l.x.n_slots) std::memset(c.l.x.conns, 0, (uint64_t)c.l.x.n_slots * sizeof(fs_accept_conn));
             if (c.l.x.n_listeners) std::memset(c.l.x.listeners_out, 0, (uint64_t)c.l.x.n_listeners * sizeof(fs_listener_out));
         }
-        if (c.kind == rxp::kClose) {  // no connection has a flow
+        if (c.kind >= rxp::kClose) {  // no connection has a flow
             for (uint32_t i = 0; i < c.k.y.n_closers; ++i) c.k.y.closers_out[i] = cl::untouched_closer(c.k.closers[i]);
             for (uint32_t i = 0; i < s.n_socks; ++i)
                 c.k.y.socks_close[i] = cl::untouched_sock(s.socks[i].rcv_nxt, s.snd[i].snd_una, s.snd[i].snd_wnd, cl::kNone);
         }
+        // no opener has a flow either, yet a flagged one owes its SYN, which only the device builds
+        if (c.kind == rxp::kConnect && c.o.z.n_openers != 0) return connect_host_empty(ctx, c);
         return FS_SUCCESS;
     }
     // the accept call's own arrays, as the caller passed them, in plan::rx::AcceptArray's order
-    const bool accepts = c.kind >= rxp::kAccept, closes = c.kind == rxp::kClose;
+    const bool accepts = c.kind >= rxp::kAccept, closes = c.kind >= rxp::kClose, connects = c.kind == rxp::kConnect;
     const framesum::RxAccept& hx = c.l.x;
     void* const h_accept[rxp::kAcceptArrays] = {hx.conns, hx.listeners_out, hx.accept_of, hx.synacks, hx.synack_out, hx.synack_status};
     // the close call's own arrays likewise, in plan::rx::CloseArray's order
     const framesum::RxClose& hy = c.k.y;
     void* const h_close[rxp::kCloseArrays] = {hy.closers_out, hy.socks_close, hy.ctl_code};
+    // the connect call's own arrays likewise, in plan::rx::ConnectArray's order
+    const framesum::RxConnect& hz = c.o.z;
+    void* const h_connect[rxp::kConnectArrays] = {hz.openers_out, hz.replies, hz.reply_out, hz.reply_status};
     const framesum::plan::Scan sc = framesum::plan::scan_batch(b.offsets, b.lengths, n, frames_bytes);
     if (sc.bad < n) return invalid(ctx, c, "frame " + std::to_string(sc.bad) + " ends past frames_bytes");
     // the device payload buffer: payload_cap, or the most payload the batch can hold when that is less
@@ -356,13 +453,14 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     const rxp::Layout L = rxp::layout(c.kind, n, s.n_socks);
     const rxp::AcceptLayout AL = rxp::accept_layout(L.bytes, n, hx.n_listeners, hx.n_slots);
     const rxp::CloseLayout CL = rxp::close_layout(AL.bytes, n, s.n_socks, hy.n_closers);
+    const rxp::ConnectLayout NL = rxp::connect_layout(CL.bytes, hz.n_openers);
     fs_status st = begin_host_call(ctx);
     if (st == FS_SUCCESS && sockets) st = ctx->dl_rings.grow(ctx, span);
     // (the socket calls begin once more, behind the rings' buffer: a second hipSetDevice that keeps their
     // sequence of HIP calls what profiles/rx_call_refactor/calls.txt compares)
     if (st == FS_SUCCESS && sockets) st = begin_host_call(ctx);
     if (st == FS_SUCCESS) st = ctx->co_payload.grow(ctx, d_cap);
-    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, closes ? CL.bytes : accepts ? AL.bytes : L.bytes);
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, connects ? NL.bytes : closes ? CL.bytes : accepts ? AL.bytes : L.bytes);
     if (st != FS_SUCCESS) return st;
     Staged sg;
     st = stage_batch(ctx, b.frames, frames_bytes, sc.lo, sc.hi, b.offsets, b.lengths, n, sg);
@@ -395,6 +493,14 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
         if (h_close[a] && CL.room[a] != 0) d_close[a] = ctx->rx_arrays.p + CL.at[a];
     d.y = framesum::RxClose{hy.n_socks, hy.n_closers, static_cast<fs_cl_out*>(d_close[rxp::kClosersOut]),
                             static_cast<fs_cl_out*>(d_close[rxp::kSocksClose]), static_cast<uint8_t*>(d_close[rxp::kCtlCode])};
+    void* d_connect[rxp::kConnectArrays] = {};
+    for (uint32_t a = 0; connects && a < rxp::kConnectArrays; ++a) {
+        if (!h_connect[a] || NL.room[a] == 0) continue;
+        d_connect[a] = ctx->rx_arrays.p + NL.at[a];
+        if (rxp::kConnectArrayDesc[a].goes_in)
+            FS_HIP_DRAIN(ctx, hipMemcpyAsync(d_connect[a], h_connect[a], NL.room[a], hipMemcpyHostToDevice, sg.ks));
+    }
+    d.z = connect_device(hz, d_connect, d.y.ctl_code);
     RxLeft left;
     st = rx_run(ctx, c, d, left);
     if (st != FS_SUCCESS) {
@@ -426,6 +532,8 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
         FS_HIP_DRAIN(ctx, back(d_accept[a] ? h_accept[a] : nullptr, d_accept[a], AL.room[a]));
     for (uint32_t a = 0; closes && a < rxp::kCloseArrays; ++a)
         FS_HIP_DRAIN(ctx, back(d_close[a] ? h_close[a] : nullptr, d_close[a], CL.room[a]));
+    for (uint32_t a = 0; connects && a < rxp::kConnectArrays; ++a)
+        FS_HIP_DRAIN(ctx, back(d_connect[a] ? h_connect[a] : nullptr, d_connect[a], NL.room[a]));
     FS_HIP_DRAIN(ctx, back(s.n_socks ? h.rings + s.span.lo : nullptr, ctx->dl_rings.p, span));
     FS_HIP_DRAIN(ctx, back(h.out, sg.d_out, (uint64_t)n * sizeof(fs_digest)));
     FS_HIP_DRAIN(ctx, back(h.status, sg.d_st, n));
@@ -436,7 +544,7 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
 
 }  // namespace
 
-// ---- The twelve entry points: fill the record, check, run.
+// ---- The fourteen entry points: fill the record, check, run.
 
 fs_status fs_coalesce_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
                             uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
@@ -648,6 +756,62 @@ fs_status fs_close_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t
     c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
                 synack_status);
     c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
+    const fs_status st = rx_check(ctx, c, false);
+    return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
+}
+
+fs_status fs_connect_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                               uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
+                               uint8_t* rings, uint64_t rings_bytes, fs_rx_sock_out* socks_out, uint8_t* delivered,
+                               const fs_rx_snd* snd, fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                               uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots, uint32_t synack_flags,
+                               fs_accept_conn* conns, fs_listener_out* listeners_out, uint32_t* accept_of,
+                               uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status, const fs_cl_sock* closers,
+                               uint32_t n_closers, fs_cl_out* closers_out, fs_cl_out* socks_close, uint8_t* ctl_code,
+                               const fs_cn_sock* openers, uint32_t n_openers, uint32_t reply_flags, fs_cn_out* openers_out,
+                               uint8_t* replies, fs_digest* reply_out, uint8_t* reply_status,
+                               uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order,
+                               uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kConnect, "fs_connect_flows_batch", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
+    c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
+    c.opening(openers, n_openers, reply_flags, openers_out, replies, reply_out, reply_status);
+    const fs_status st = rx_check(ctx, c, true);
+    return st != FS_SUCCESS ? st : rx_device(ctx, c, stream);
+}
+
+fs_status fs_connect_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                                    const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags,
+                                    const fs_rx_sock* socks, uint32_t n_socks, uint8_t* rings, uint64_t rings_bytes,
+                                    fs_rx_sock_out* socks_out, uint8_t* delivered, const fs_rx_snd* snd,
+                                    fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                                    uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots,
+                                    uint32_t synack_flags, fs_accept_conn* conns, fs_listener_out* listeners_out,
+                                    uint32_t* accept_of, uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status,
+                                    const fs_cl_sock* closers, uint32_t n_closers, fs_cl_out* closers_out,
+                                    fs_cl_out* socks_close, uint8_t* ctl_code, const fs_cn_sock* openers,
+                                    uint32_t n_openers, uint32_t reply_flags, fs_cn_out* openers_out, uint8_t* replies,
+                                    fs_digest* reply_out, uint8_t* reply_status, uint8_t* payload, uint64_t payload_cap,
+                                    fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
+                                    fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kConnect, "fs_connect_flows_batch_host", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
+    c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
+    c.opening(openers, n_openers, reply_flags, openers_out, replies, reply_out, reply_status);
     const fs_status st = rx_check(ctx, c, false);
     return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
 }

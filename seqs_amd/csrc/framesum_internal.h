@@ -11,6 +11,7 @@
 #include "../../include/framesum_recv.h"
 #include "../../include/framesum_accept.h"
 #include "../../include/framesum_close.h"
+#include "../../include/framesum_connect.h"
 #include "framesum_choice.h"
 #include "framesum_plan.h"
 
@@ -101,10 +102,10 @@ hipError_t launch_send_rings(const uint8_t* d_block, const segment::Block& b, ui
                              int workgroups, hipStream_t stream);
 
 // ---- The RX calls (framesum_coalesce.hip, framesum_flows.hip, framesum_deliver.hip, framesum_recv.hip,
-// framesum_accept.hip, framesum_close.hip). A call is a row of stages on one stream -- the digest launch and
-// the plain or the flow-aware gather, then the delivery, then the receive call's fold, then the accept
-// call's passive open, then the close call's control walks -- each behind the one before it and reading
-// what it left. The launches take the call as a few records.
+// framesum_accept.hip, framesum_close.hip, framesum_connect.hip). A call is a row of stages on one stream --
+// the digest launch and the plain or the flow-aware gather, then the delivery, then the receive call's fold,
+// then the accept call's passive open, then the close call's control walks, then the connect call's active
+// open -- each behind the one before it and reading what it left. The launches take the call as a few records.
 
 // The batch as the launches read it.
 struct RxBatch {
@@ -178,7 +179,12 @@ FlowScratch flows_scratch(uint32_t n);
 DeliverScratch deliver_scratch(uint32_t n, uint32_t n_socks);
 RecvScratch recv_scratch(uint32_t n);
 AcceptScratch accept_scratch(uint32_t n, uint32_t n_listeners, uint32_t n_slots);
+// ConnectScratch: 16-byte aligned; 20 bytes per frame and 92 per opener.
+struct ConnectScratch {
+    uint64_t sq, reprec, flow_opener, opener_first, bytes;
+};
 CloseScratch close_scratch(uint32_t n, uint32_t n_closers);
+ConnectScratch connect_scratch(uint32_t n, uint32_t n_openers);
 
 // What the accept call has beside a receive call's batch and results: the counts of its staged lists and
 // where its own results go on the device (the caller's pointers in the device form, the context's device
@@ -202,6 +208,17 @@ struct RxClose {
     uint8_t* ctl_code;
 };
 
+// What the connect call has beside a close call's: the count of its list and where its own results go on
+// the device (reply_out and reply_status are nullable); ctl_code is the close call's array.
+struct RxConnect {
+    uint32_t n_openers, reply_flags;
+    fs_cn_out* openers_out;
+    uint8_t* replies;
+    fs_digest* reply_out;
+    uint8_t* reply_status;
+    uint8_t* ctl_code;
+};
+
 // What the stages of one call leave on the device for the stages behind them: each stage's scratch, laid
 // out as its layout says (all zero for a stage that has not run: an empty batch has no flow stage), and
 // where the gather's count of written payload bytes lies.
@@ -217,6 +234,8 @@ struct RxLeft {
     AcceptScratch acs;
     uint8_t* close_scratch;
     CloseScratch cs;
+    uint8_t* connect_scratch;
+    ConnectScratch cns;
 };
 
 // The launches that follow a batch's digest launch on the stream (fs_coalesce_batch in
@@ -254,5 +273,12 @@ hipError_t launch_accept(const RxBatch& b, const RxAccept& x, const RxLeft& left
 // socket. y.ctl_code is zeroed by the caller. With n of 0 only the out records are written.
 hipError_t launch_close(const RxBatch& b, const RxResults& r, const RxClose& y, const RxLeft& left, const uint8_t* d_block,
                         const RxLaunch& how);
+
+// The launches that follow a batch's close launches (fs_connect_flows_batch in include/framesum_connect.h)
+// and read what the flow launches left. `d_block`: the device copy of the staged block (framesum_connect.h
+// block_of: the openers, then their table); at least one opener. `tables` and `tx_workgroups`: as
+// launch_accept's, for the reply kernel. With n of 0 only the out records and the flagged SYNs are written.
+hipError_t launch_connect(const RxBatch& b, const RxResults& r, const RxConnect& z, const RxLeft& left, const uint8_t* d_block,
+                          const SegTables* tables, int tx_workgroups, const RxLaunch& how);
 
 }  // namespace framesum

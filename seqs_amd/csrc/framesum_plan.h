@@ -217,17 +217,17 @@ inline void host_chunks(const uint64_t* offsets, const uint32_t* lengths, uint32
 }
 
 // ---------------------------------------------------------------------------------------
-// The device result arrays of the six RX host forms (fs_coalesce_batch_host,
+// The device result arrays of the seven RX host forms (fs_coalesce_batch_host,
 // fs_coalesce_flows_batch_host, fs_deliver_flows_batch_host, fs_recv_flows_batch_host and, with the
-// arrays of their own in the second and the third table below, fs_accept_flows_batch_host and
-// fs_close_flows_batch_host), described
+// arrays of their own in the second, the third and the fourth table below, fs_accept_flows_batch_host,
+// fs_close_flows_batch_host and fs_connect_flows_batch_host), described
 // once: which arrays a call kind has, what each is sized by, where each lies in the context's one
 // buffer, and how much of each comes back given the totals the device reported. The host forms carve
 // the buffer and copy back by walking this description (framesum_api_rx.cpp).
 namespace rx {
 
 // A kind has the arrays of the kinds before it and its own.
-enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv, kAccept, kClose };
+enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv, kAccept, kClose, kConnect };
 enum Array : uint32_t { kTotals, kRuns, kFlowRecs, kOrder, kRunOf, kDelivered, kSocksOut, kSndOut, kCode, kArrays };
 // What counts an array's entries: one record, the batch's frames, the call's sockets, or (for what
 // comes back only) one of the totals.
@@ -355,6 +355,39 @@ inline CloseLayout close_layout(uint64_t base, uint64_t n, uint64_t n_socks, uin
         at = (at + d.align - 1) / d.align * d.align;
         L.at[a] = at;
         L.room[a] = d.elem * (d.count == kPerCloser ? n_closers : d.count == kPerSockOfCall ? n_socks : n);
+        at += L.room[a];
+    }
+    L.bytes = at;
+    return L;
+}
+
+// The seventh kind's own arrays (fs_connect_flows_batch_host: the kind has every array above, and these),
+// in a fourth table: each lies behind the close call's arrays in the same buffer; the reply arrays go to
+// the device first (the call writes only the entries of openers with a reply), and every one comes back
+// whole.
+enum ConnectArray : uint32_t { kOpenersOut, kReplies, kReplyOut, kReplyStatus, kConnectArrays };
+struct ConnectArrayDesc {
+    uint32_t elem, align;  // bytes per opener, and the alignment the kernels' stores want
+    bool goes_in;
+};
+constexpr ConnectArrayDesc kConnectArrayDesc[kConnectArrays] = {
+    {48, 4, false},  // fs_cn_out
+    {64, 1, true},   // replies (FS_ACCEPT_STRIDE)
+    {8, 8, true},    // reply_out
+    {1, 1, true},    // reply_status
+};
+struct ConnectLayout {
+    uint64_t at[kConnectArrays], room[kConnectArrays], bytes;  // `bytes`: the arrays above and these
+};
+// `base`: close_layout(...).bytes (0 for a call without a batch: these arrays alone).
+inline ConnectLayout connect_layout(uint64_t base, uint64_t n_openers) {
+    ConnectLayout L;
+    uint64_t at = base;
+    for (uint32_t a = 0; a < kConnectArrays; ++a) {
+        const ConnectArrayDesc& d = kConnectArrayDesc[a];
+        at = (at + d.align - 1) / d.align * d.align;
+        L.at[a] = at;
+        L.room[a] = d.elem * n_openers;
         at += L.room[a];
     }
     L.bytes = at;

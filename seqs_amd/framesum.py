@@ -26,6 +26,8 @@ from .abi import (  # noqa: F401 (re-exported: this module is the binding's publ
     CLOSE_ACK_OWED, CLOSE_DATA, CLOSE_EXPECTED, CLOSE_FIN, CLOSE_IGNORED, CLOSE_KEEPALIVE, CLOSE_MAX_CLOSERS, CLOSE_NONE,
     CLOSE_OUT_DTYPE, CLOSE_PROTOTYPES, CLOSE_REJECTED, CLOSE_RESET, CLOSE_RST, CLOSE_TAKEN, CLOSER_DTYPE,
     ST_CLOSED, ST_CLOSE_WAIT, ST_CLOSING, ST_ESTABLISHED, ST_FIN_WAIT_1, ST_FIN_WAIT_2, ST_LAST_ACK, ST_TIME_WAIT,
+    CN_BAD_ACK, CN_REPLY_ACK, CN_REPLY_NONE, CN_REPLY_RST, CN_REPLY_SYN, CN_REPLY_SYNACK, CN_SEND_SYN, CN_STOP_RST, CN_STOP_SYN,
+    CONNECT_MAX_OPENERS, CONNECT_OUT_DTYPE, CONNECT_PROTOTYPES, OPENER_DTYPE, ST_LISTEN, ST_SYN_RCVD, ST_SYN_SENT,
     DELIVER_MAX_SOCKS, DELIVER_PROTOTYPES, DIGEST_DTYPE, EXPORTED_SYMBOLS, FCS_APPEND, FILL_CSUM, FLOW_DTYPE,
     FLOW_TOTALS_DTYPE, FS_E_HIP, FS_E_INVALID, FS_E_NODEVICE, FS_E_NOMEM, FS_ERR_FCS, FS_SUCCESS, NO_FLOW, NO_RUN,
     PROTOTYPES, RECV_ACK_OWED, RECV_DUPLICATE, RECV_FIN, RECV_KEEPALIVE, RECV_NONE, RECV_PROTOTYPES, RECV_REJECTED,
@@ -90,6 +92,7 @@ _RX_DELIVER = ("fs_deliver_flows_batch", *_RX_FLOWS[1:])
 _RX_RECV = ("fs_recv_flows_batch", *_RX_FLOWS[1:])  # (the delivery call with snd, snd_out and code behind delivered)
 _RX_ACCEPT = ("fs_accept_flows_batch", *_RX_FLOWS[1:])  # (the receive call with the listening arguments behind code)
 _RX_CLOSE = ("fs_close_flows_batch", *_RX_FLOWS[1:])  # (the accept call with the closing arguments behind synack_status)
+_RX_CONNECT = ("fs_connect_flows_batch", *_RX_FLOWS[1:])  # (the close call with the opening arguments behind ctl_code)
 
 
 @dataclass
@@ -620,12 +623,24 @@ class Engine(_Handle):
                 ptr(of), ptr(synacks), ptr(syn_out), ptr(syn_st))
         rx, mine = _RX_ACCEPT, ()
         if _closing is not None:  # close_flows_device: the closing arguments behind synack_status, its tensors in front
-            closers, ctl = _closing
+            closers, ctl = _closing[:2]
             closers_out = torch.empty((int(closers.size), CLOSE_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
             socks_close = torch.empty((int(socks.size), CLOSE_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
             ctl_code = torch.empty((n,), dtype=torch.uint8, device=dev) if ctl else None
             args += (_array_ptr(closers), int(closers.size), ptr(closers_out), ptr(socks_close), ptr(ctl_code))
             rx, mine = _RX_CLOSE, (closers_out, socks_close, ctl_code)
+            if len(_closing) > 2:  # connect_flows_device: the opening arguments behind ctl_code, its tensors in front
+                openers, reply_flags, replies, reply_results = _closing[2]
+                n_open = int(openers.size)
+                if replies is None:
+                    replies = torch.zeros((n_open * ACCEPT_STRIDE,), dtype=torch.uint8, device=dev)
+                assert replies.is_cuda and replies.dtype == torch.uint8 and replies.is_contiguous()
+                assert replies.numel() >= n_open * ACCEPT_STRIDE, "replies holds ACCEPT_STRIDE bytes per opener"
+                openers_out = torch.empty((n_open, CONNECT_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                rep_out = torch.zeros((n_open, 2), dtype=torch.int32, device=dev) if reply_results else None
+                rep_st = torch.zeros((n_open,), dtype=torch.uint8, device=dev) if reply_results else None
+                args += (_array_ptr(openers), n_open, reply_flags, ptr(openers_out), ptr(replies), ptr(rep_out), ptr(rep_st))
+                rx, mine = _RX_CONNECT, (openers_out, replies, rep_out, rep_st, *mine)
         return (*mine, conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
                 *self._rx_device(rx, frames, offsets, lengths, mtu, flags, payload, stream, args))
 
@@ -676,12 +691,24 @@ class Engine(_Handle):
                 ptr(of), ptr(synacks), ptr(syn_out), ptr(syn_st))
         rx, mine = _RX_ACCEPT, ()
         if _closing is not None:  # close_flows_host
-            closers, ctl = _closing
+            closers, ctl = _closing[:2]
             closers_out = np.zeros(int(closers.size), dtype=CLOSE_OUT_DTYPE)
             socks_close = np.zeros(int(socks.size), dtype=CLOSE_OUT_DTYPE)
             ctl_code = np.zeros(n, dtype=np.uint8) if ctl else None
             args += (_array_ptr(closers), int(closers.size), ptr(closers_out), ptr(socks_close), ptr(ctl_code))
             rx, mine = _RX_CLOSE, (closers_out, socks_close, ctl_code)
+            if len(_closing) > 2:  # connect_flows_host
+                openers, reply_flags, replies, reply_results = _closing[2]
+                n_open = int(openers.size)
+                if replies is None:
+                    replies = np.zeros(n_open * ACCEPT_STRIDE, dtype=np.uint8)
+                assert isinstance(replies, np.ndarray) and replies.dtype == np.uint8 and replies.flags["C_CONTIGUOUS"]
+                assert replies.flags["WRITEABLE"] and replies.size >= n_open * ACCEPT_STRIDE
+                openers_out = np.zeros(n_open, dtype=CONNECT_OUT_DTYPE)
+                rep_out = np.zeros(n_open, dtype=DIGEST_DTYPE) if reply_results else None
+                rep_st = np.zeros(n_open, dtype=np.uint8) if reply_results else None
+                args += (_array_ptr(openers), n_open, reply_flags, ptr(openers_out), ptr(replies), ptr(rep_out), ptr(rep_st))
+                rx, mine = _RX_CONNECT, (openers_out, replies, rep_out, rep_st, *mine)
         return (*mine, conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
                 *self._rx_host(rx, frames, offsets, lengths, mtu, flags, payload, args))
 
@@ -713,6 +740,39 @@ class Engine(_Handle):
         closers = np.ascontiguousarray(closers, dtype=CLOSER_DTYPE)
         return self.accept_flows_host(frames, offsets, lengths, socks, snd, rings, listeners, slots,
                                       _closing=(closers, ctl_code), **kw)
+
+    # ---- the connect call: the close call plus the active open (include/framesum_connect.h) ----
+    def connect_flows_device(self, frames, offsets, lengths, socks: np.ndarray, snd: np.ndarray, rings,
+                             listeners: np.ndarray, slots: np.ndarray, closers: np.ndarray, openers: np.ndarray,
+                             reply_flags: int = 0, replies=None, reply_results: bool = True, ctl_code: bool = True, **kw):
+        """close_flows_device plus the receive side of SynSent (fs_connect_flows_batch): `openers` is an
+        OPENER_DTYPE array on the host, the connections that have sent or are about to send their SYN (key,
+        CN_SEND_SYN or 0, the two MACs, iss, rcv_wnd, the IPv4 ID seed). Every opener's flow is walked under
+        the rule of the header, and the control frame the opener owes is built. `replies`: a uint8 CUDA
+        tensor of n_openers * ACCEPT_STRIDE bytes (else a new zeroed one), of which only the 54 (58 with
+        reply_flags FCS_APPEND) frame bytes of openers with a reply are written. Further keyword arguments
+        are accept_flows_device's. Returns (openers_out, replies, reply_out, reply_status, then
+        close_flows_device's tuple) device tensors: openers_out (n_openers, 48) uint8 = CONNECT_OUT_DTYPE
+        records, reply_out (n_openers, 2) int32 and reply_status (n_openers,) uint8 as digest_device gives
+        them, written for openers with a reply only (zeroed here first; None when `reply_results` is
+        False). Asynchronous on `stream`; split_connect() brings the records to the host."""
+        closers = np.ascontiguousarray(closers, dtype=CLOSER_DTYPE)
+        openers = np.ascontiguousarray(openers, dtype=OPENER_DTYPE)
+        return self.accept_flows_device(frames, offsets, lengths, socks, snd, rings, listeners, slots,
+                                        _closing=(closers, ctl_code, (openers, reply_flags, replies, reply_results)), **kw)
+
+    def connect_flows_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, socks: np.ndarray,
+                           snd: np.ndarray, rings: np.ndarray, listeners: np.ndarray, slots: np.ndarray,
+                           closers: np.ndarray, openers: np.ndarray, reply_flags: int = 0, replies=None,
+                           reply_results: bool = True, ctl_code: bool = True, **kw):
+        """connect_flows_device from and to host memory (fs_connect_flows_batch_host). `replies`: a writable
+        uint8 array of n_openers * ACCEPT_STRIDE bytes (else a new zeroed one), written in place. Returns
+        (openers_out CONNECT_OUT_DTYPE[n_openers], replies, reply_out DIGEST_DTYPE[n_openers] or None,
+        reply_status uint8[n_openers] or None, then close_flows_host's tuple)."""
+        closers = np.ascontiguousarray(closers, dtype=CLOSER_DTYPE)
+        openers = np.ascontiguousarray(openers, dtype=OPENER_DTYPE)
+        return self.accept_flows_host(frames, offsets, lengths, socks, snd, rings, listeners, slots,
+                                      _closing=(closers, ctl_code, (openers, reply_flags, replies, reply_results)), **kw)
 
     # ---- TCP segments from socket TX rings (include/framesum_send.h) ------------
     @staticmethod
@@ -976,6 +1036,54 @@ def split_close(closers_out, socks_close, ctl_code=None):
     for them): (CLOSE_OUT_DTYPE[n_closers], CLOSE_OUT_DTYPE[n_socks], uint8[n] or None)."""
     return (_records(closers_out, CLOSE_OUT_DTYPE), _records(socks_close, CLOSE_OUT_DTYPE),
             None if ctl_code is None else _records(ctl_code, np.uint8))
+
+
+def split_connect(openers_out, reply_out=None, reply_status=None):
+    """The host view of connect_flows_device's `openers_out`, `reply_out` and `reply_status` tensors (this
+    waits for them): (CONNECT_OUT_DTYPE[n_openers], DIGEST_DTYPE[n_openers] or None, uint8[n_openers] or
+    None)."""
+    return (_records(openers_out, CONNECT_OUT_DTYPE), None if reply_out is None else _records(reply_out, DIGEST_DTYPE),
+            None if reply_status is None else _records(reply_status, np.uint8))
+
+
+def socks_from_connect(openers, out, ring_off=0, ring_size=0, mss: int = 1460):
+    """How the openers that left SynSent in a connect call are listed for the next calls: the counterpart
+    of socks_from_accept. `openers`: the OPENER_DTYPE rows the call was given, `out` its CONNECT_OUT_DTYPE
+    records for them (host array); `ring_off` and `ring_size`: per opener (an array of n_openers entries,
+    or one value for all) where the connection's RX ring lies in `rings`. Returns (idx, socks, snd, tx)
+    for the openers that came back ST_ESTABLISHED or ST_SYN_RCVD, in opener order: idx their indices; socks
+    SOCK_DTYPE rows (key, rcv_nxt, rcv_wnd, snd_nxt = iss + 1: the reply has gone out, a SYN-ACK's SYN
+    included; an empty ring); snd SND_DTYPE rows {snd_una, snd_wnd} of the record (a SynRcvd row's snd_una
+    is iss, so that the peer's ACK is code 1 with snd_una == iss + 1, as behind an accept call); tx
+    TX_SOCK_DTYPE rows whose 54-byte header template is the reply's (the two MACs, addresses and ports
+    swapped from the key, the ID seed advanced past the reply, mss = the peer's or `mss` when its SYN had
+    none, the send state snd_una = snd_nxt = iss + 1)."""
+    openers = np.atleast_1d(np.asarray(openers, dtype=OPENER_DTYPE))
+    out = np.atleast_1d(np.asarray(out, dtype=CONNECT_OUT_DTYPE))
+    assert openers.size == out.size, "one connect record per opener"
+    idx = np.flatnonzero((out["state"] == ST_ESTABLISHED) | (out["state"] == ST_SYN_RCVD))
+    ring_off = np.broadcast_to(np.asarray(ring_off, dtype=np.uint64), (openers.size,))[idx]
+    ring_size = np.broadcast_to(np.asarray(ring_size, dtype=np.uint32), (openers.size,))[idx]
+    s, o = openers[idx], out[idx]
+    nxt = s["iss"] + np.uint32(1)
+    socks = np.zeros(idx.size, dtype=SOCK_DTYPE)
+    socks["key"], socks["rcv_nxt"], socks["rcv_wnd"], socks["snd_nxt"] = s["key"], o["rcv_nxt"], s["rcv_wnd"], nxt
+    socks["ring_size"], socks["ring_off"], socks["ring_wpos"], socks["ring_free"] = ring_size, ring_off, 0, ring_size
+    snd = np.zeros(idx.size, dtype=SND_DTYPE)
+    snd["snd_una"], snd["snd_wnd"] = o["snd_una"], o["snd_wnd"]
+    tx = np.zeros(idx.size, dtype=TX_SOCK_DTYPE)
+    hdr = tx["hdr"]
+    hdr[:, 0:6], hdr[:, 6:12] = s["remote_mac"], s["local_mac"]
+    hdr[:, 12], hdr[:, 14], hdr[:, 22], hdr[:, 23], hdr[:, 46] = 0x08, 0x45, 64, 6, 0x50
+    for k in range(idx.size):  # the ID the connection's next frame carries: two steps past the seed
+        nid = _prand16(_prand16(int(s["ip_id"][k])))
+        hdr[k, 18], hdr[k, 19] = nid >> 8, nid & 0xFF
+    hdr[:, 26:30], hdr[:, 30:34] = s["key"][:, 5:9], s["key"][:, 1:5]
+    hdr[:, 34:36], hdr[:, 36:38] = s["key"][:, 11:13], s["key"][:, 9:11]
+    tx["mss"] = np.minimum(np.where(o["peer_mss"] != 0, o["peer_mss"], mss), 65495)  # (the ring send's largest chunk)
+    tx["snd_una"] = tx["snd_nxt"] = nxt
+    tx["snd_wnd"], tx["rcv_nxt"], tx["rcv_wnd"] = o["snd_wnd"], o["rcv_nxt"], s["rcv_wnd"]
+    return idx, socks, snd, tx
 
 
 def closers_from(socks, socks_close) -> tuple:
