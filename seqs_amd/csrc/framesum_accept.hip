@@ -185,23 +185,22 @@ hipError_t launch_accept(const RxBatch& b, const RxAccept& x, const RxLeft& left
     a.listeners_out = x.listeners_out;
     a.accept_of = x.accept_of;
     a.n = n;
-    a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
+    const ScanGrid g = scan_grid(n, how);
+    a.n_blocks = g.blocks;
     a.n_socks = x.n_socks;
     a.n_listeners = x.n_listeners;
     a.n_slots = x.n_slots;
     a.tmask = flows::table_slots(x.n_listeners) - 1u;
     a.hash_mask = how.hash_mask;
     a.lb = flows::index_bits(x.n_listeners);
-    const uint32_t cap = (uint32_t)(how.max_workgroups > 0 ? how.max_workgroups : 1);
-    const uint32_t scan_grid = a.n_blocks < cap ? a.n_blocks : cap;
     hipError_t e = hipMemsetAsync(a.rank_in, 0xFF, 8ull * n, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(accept_mark, dim3(scan_grid), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(accept_mark, dim3(g.scan), dim3(kThreads), 0, stream, a);
     size_t sort_bytes = s.sort_bytes;
     e = sort_keys(scratch + s.sort_temp, sort_bytes, a.rank_in, reinterpret_cast<uint64_t*>(scratch + s.rank_sorted), n,
                   ac::rank_bits(a.b, x.n_listeners), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(accept_assign, dim3(scan_grid), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(accept_assign, dim3(g.scan), dim3(kThreads), 0, stream, a);
     if (x.n_slots != 0) {
         const ctlframe::Args sa = ctlframe::args_of(a.synrec, x.n_slots, x.synacks, x.synack_out, x.synack_status, tables,
                                                     b.mtu, x.synack_flags);

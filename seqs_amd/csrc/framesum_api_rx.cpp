@@ -44,30 +44,20 @@ namespace cn = framesum::connect;
 
 namespace {
 
-// The listening part of an accept call: the caller's lists, where its own results go (x: the caller's
-// pointers, host or device as the form has them), and the listener table check_accept builds.
-struct RxListen {
-    const fs_listener* listeners = nullptr;
+// A list of an accept, a close or a connect call: the caller's records, where the call's own results go (`dev`:
+// the caller's pointers, host or device as the form has them, with the list's counts), and the table the list's
+// check builds. l: the listeners (with their second list, the slots), k: the closers, o: the openers.
+template <class Rec, class Dev>
+struct RxList {
+    const Rec* recs = nullptr;
+    Dev dev{};
+    std::vector<uint32_t> table;
+};
+struct RxListen : RxList<fs_listener, framesum::RxAccept> {
     const fs_accept_slot* slots = nullptr;
-    framesum::RxAccept x{};
-    std::vector<uint32_t> table;
 };
-
-// The closing part of a close call: the caller's list, where its own results go (y: the caller's
-// pointers, host or device as the form has them), and the closer table check_closers builds.
-struct RxClosing {
-    const fs_cl_sock* closers = nullptr;
-    framesum::RxClose y{};
-    std::vector<uint32_t> table;
-};
-
-// The opening part of a connect call: the caller's list, where its own results go (z: the caller's
-// pointers, host or device as the form has them), and the opener table check_openers builds.
-struct RxOpening {
-    const fs_cn_sock* openers = nullptr;
-    framesum::RxConnect z{};
-    std::vector<uint32_t> table;
-};
+using RxClosing = RxList<fs_cl_sock, framesum::RxClose>;
+using RxOpening = RxList<fs_cn_sock, framesum::RxConnect>;
 
 // The socket part of a delivery or a receive call: the caller's lists, and what check_socks makes of
 // them (the socket table, the span of `rings` the listed rings cover).
@@ -108,19 +98,19 @@ struct RxCall {
     void listening(const fs_listener* listeners, uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots,
                    uint32_t synack_flags, fs_accept_conn* conns, fs_listener_out* listeners_out, uint32_t* accept_of,
                    uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status) {
-        l.listeners = listeners, l.slots = slots;
-        l.x = framesum::RxAccept{s.n_socks, n_listeners, n_slots, synack_flags, conns, listeners_out,
+        l.recs = listeners, l.slots = slots;
+        l.dev = framesum::RxAccept{s.n_socks, n_listeners, n_slots, synack_flags, conns, listeners_out,
                                  accept_of,  synacks,     synack_out, synack_status};
     }
     void closing(const fs_cl_sock* closers, uint32_t n_closers, fs_cl_out* closers_out, fs_cl_out* socks_close,
                  uint8_t* ctl_code) {
-        k.closers = closers;
-        k.y = framesum::RxClose{s.n_socks, n_closers, closers_out, socks_close, ctl_code};
+        k.recs = closers;
+        k.dev = framesum::RxClose{s.n_socks, n_closers, closers_out, socks_close, ctl_code};
     }
     void opening(const fs_cn_sock* openers, uint32_t n_openers, uint32_t reply_flags, fs_cn_out* openers_out, uint8_t* replies,
                  fs_digest* reply_out, uint8_t* reply_status) {
-        o.openers = openers;
-        o.z = framesum::RxConnect{n_openers, reply_flags, openers_out, replies, reply_out, reply_status, k.y.ctl_code};
+        o.recs = openers;
+        o.dev = framesum::RxConnect{n_openers, reply_flags, openers_out, replies, reply_out, reply_status, k.dev.ctl_code};
     }
 };
 // The call as the launches see it: in the device forms the caller's batch and arrays on the caller's
@@ -167,15 +157,15 @@ fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
     if (c.kind >= rxp::kAccept) {  // the listener and slot lists' checks (framesum_accept.h), which also build the table
         RxListen& l = c.l;
         const ac::CheckAccept ca =
-            ac::check_accept(l.listeners, l.x.n_listeners, l.slots, l.x.n_slots, l.x.synack_flags, l.x.conns != nullptr,
-                             l.x.listeners_out != nullptr, l.x.synacks != nullptr, ctx->flow_hash_mask, l.table);
+            ac::check_accept(l.recs, l.dev.n_listeners, l.slots, l.dev.n_slots, l.dev.synack_flags, l.dev.conns != nullptr,
+                             l.dev.listeners_out != nullptr, l.dev.synacks != nullptr, ctx->flow_hash_mask, l.table);
         if (ca.bad != ac::kAcceptGood)
             return invalid(ctx, c, "listener or slot " + std::to_string(ca.index) + ": " + ac::bad_accept_text(ca.bad));
     }
     if (c.kind >= rxp::kClose) {  // the closer list's checks (framesum_close.h), which also build the table
         RxClosing& k = c.k;
         const cl::CheckClose cc =
-            cl::check_closers(k.closers, k.y.n_closers, k.y.closers_out != nullptr, k.y.socks_close != nullptr, c.s.socks,
+            cl::check_closers(k.recs, k.dev.n_closers, k.dev.closers_out != nullptr, k.dev.socks_close != nullptr, c.s.socks,
                               c.s.n_socks, c.s.table.data(), ctx->flow_hash_mask, k.table);
         if (cc.bad != cl::kCloseGood)
             return invalid(ctx, c, "closer " + std::to_string(cc.index) + ": " + cl::bad_close_text(cc.bad));
@@ -183,8 +173,8 @@ fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
     if (c.kind == rxp::kConnect) {  // the opener list's checks (framesum_connect.h), which also build the table
         RxOpening& o = c.o;
         const cn::CheckConnect co =
-            cn::check_openers(o.openers, o.z.n_openers, o.z.reply_flags, o.z.openers_out != nullptr, o.z.replies != nullptr,
-                              c.s.socks, c.s.n_socks, c.s.table.data(), c.k.closers, c.k.y.n_closers, c.k.table.data(),
+            cn::check_openers(o.recs, o.dev.n_openers, o.dev.reply_flags, o.dev.openers_out != nullptr, o.dev.replies != nullptr,
+                              c.s.socks, c.s.n_socks, c.s.table.data(), c.k.recs, c.k.dev.n_closers, c.k.table.data(),
                               ctx->flow_hash_mask, o.table);
         if (co.bad != cn::kConnectGood)
             return invalid(ctx, c, "opener " + std::to_string(co.index) + ": " + cn::bad_connect_text(co.bad));
@@ -197,6 +187,11 @@ fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
 // The cap of the grids behind the digest launch: up to 8 workgroups of 256 lanes per CU unless
 // fs_ctx_set_workgroups caps them.
 int rx_workgroups(const fs_ctx* ctx) { return ctx->workgroups > 0 ? ctx->workgroups : 8 * ctx->num_cus; }
+// The cap of a control-frame kernel's grid (the SYN-ACKs, the replies) as the TX frame build has it: two
+// workgroups per CU (their tables fit its LDS twice) unless fs_ctx_set_workgroups asks for fewer.
+int tx_workgroups(const fs_ctx* ctx) {
+    return ctx->workgroups > 0 && ctx->workgroups < 2 * ctx->num_cus ? ctx->workgroups : 2 * ctx->num_cus;
+}
 
 // `out` and `status` of a device-resident call that passes none: the context's own.
 fs_status spare_results(fs_ctx* ctx, RxDevice& d) {
@@ -288,15 +283,12 @@ fs_status accept_stage(fs_ctx* ctx, const RxListen& l, const RxDevice& d, const 
     if (st == FS_SUCCESS) st = seg_tables(ctx);
     if (st != FS_SUCCESS) return st;
     left.accept_scratch = ctx->ac_scratch.p;
-    // the SYN-ACK kernel's grid as the TX frame build caps it: two workgroups per CU (their tables fit its
-    // LDS twice) unless fs_ctx_set_workgroups asks for fewer
-    const int tx_wgs = ctx->workgroups > 0 && ctx->workgroups < 2 * ctx->num_cus ? ctx->workgroups : 2 * ctx->num_cus;
     const ac::Block blk = ac::block_of(x.n_listeners, x.n_slots);
     const auto fill = [&](uint8_t* h_block) {
-        ac::stage(l.listeners, x.n_listeners, l.table.data(), l.slots, x.n_slots, blk, h_block);
+        ac::stage(l.recs, x.n_listeners, l.table.data(), l.slots, x.n_slots, blk, h_block);
     };
     const auto kernels = [&](const uint8_t* d_block) {
-        return framesum::launch_accept(d.b, x, left, d_block, ctx->d_seg_tables, tx_wgs, how);
+        return framesum::launch_accept(d.b, x, left, d_block, ctx->d_seg_tables, tx_workgroups(ctx), how);
     };
     return staged_launch(ctx, blk.bytes, d.stream, "fs_accept_flows_batch: launch", fill, kernels);
 }
@@ -308,13 +300,13 @@ fs_status close_stage(fs_ctx* ctx, const RxCall& c, const RxDevice& d, const RxL
     const framesum::RxClose& y = d.y;
     if (d.b.n != 0 && y.ctl_code) FS_HIP(ctx, hipMemsetAsync(y.ctl_code, 0, d.b.n, d.stream));
     if (y.n_closers == 0 && y.n_socks == 0) return FS_SUCCESS;
-    left.cs = framesum::close_scratch(d.b.n, y.n_closers);
+    left.cs = framesum::owner_scratch(d.b.n, y.n_closers);
     const fs_status st = ctx->cl_scratch.grow(ctx, left.cs.bytes);
     if (st != FS_SUCCESS) return st;
     left.close_scratch = ctx->cl_scratch.p;
     const cl::Block blk = cl::block_of(y.n_closers, y.n_socks);
     const auto fill = [&](uint8_t* h_block) {
-        cl::stage(c.k.closers, y.n_closers, c.k.table.data(), c.s.socks, y.n_socks, blk, h_block);
+        cl::stage(c.k.recs, y.n_closers, c.k.table.data(), c.s.socks, y.n_socks, blk, h_block);
     };
     const auto kernels = [&](const uint8_t* d_block) { return framesum::launch_close(d.b, d.r, y, left, d_block, how); };
     return staged_launch(ctx, blk.bytes, d.stream, "fs_close_flows_batch: launch", fill, kernels);
@@ -330,12 +322,10 @@ fs_status connect_stage(fs_ctx* ctx, const RxCall& c, const RxDevice& d, const R
     if (st == FS_SUCCESS) st = seg_tables(ctx);
     if (st != FS_SUCCESS) return st;
     left.connect_scratch = ctx->cn_scratch.p;
-    // the reply kernel's grid as the TX frame build caps it (accept_stage)
-    const int tx_wgs = ctx->workgroups > 0 && ctx->workgroups < 2 * ctx->num_cus ? ctx->workgroups : 2 * ctx->num_cus;
     const cn::Block blk = cn::block_of(z.n_openers);
-    const auto fill = [&](uint8_t* h_block) { cn::stage(c.o.openers, z.n_openers, c.o.table.data(), blk, h_block); };
+    const auto fill = [&](uint8_t* h_block) { cn::stage(c.o.recs, z.n_openers, c.o.table.data(), blk, h_block); };
     const auto kernels = [&](const uint8_t* d_block) {
-        return framesum::launch_connect(d.b, d.r, z, left, d_block, ctx->d_seg_tables, tx_wgs, how);
+        return framesum::launch_connect(d.b, d.r, z, left, d_block, ctx->d_seg_tables, tx_workgroups(ctx), how);
     };
     return staged_launch(ctx, blk.bytes, d.stream, "fs_connect_flows_batch: launch", fill, kernels);
 }
@@ -362,37 +352,70 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
 fs_status rx_device(fs_ctx* ctx, const RxCall& c, void* stream) {
     FS_HIP(ctx, hipSetDevice(ctx->device));
     RxLeft left;
-    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.x, c.k.y, c.o.z}, left);
+    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.dev, c.k.dev, c.o.dev}, left);
 }
 
-// The connect part of a host form as the launches see it: `d_connect` holds the device arrays in
-// plan::rx::ConnectArray's order (null: the caller passed none).
-framesum::RxConnect connect_device(const framesum::RxConnect& hz, void* const d_connect[rxp::kConnectArrays], uint8_t* ctl_code) {
-    return framesum::RxConnect{hz.n_openers, hz.reply_flags, static_cast<fs_cn_out*>(d_connect[rxp::kOpenersOut]),
-                               static_cast<uint8_t*>(d_connect[rxp::kReplies]), static_cast<fs_digest*>(d_connect[rxp::kReplyOut]),
-                               static_cast<uint8_t*>(d_connect[rxp::kReplyStatus]), ctl_code};
+// ---- The own arrays of the accept, the close and the connect call in a host form, walked by
+// plan::rx::kExtraArrayDesc. `h`: the caller's host pointers in that table's order (null: the caller passed none).
+struct RxExtra {
+    void* h[rxp::kExtraArrays];
+    void* d[rxp::kExtraArrays] = {};  // the device arrays, null where the call has none or the caller passed none
+    rxp::ExtraLayout L{};
+    explicit RxExtra(const RxCall& c)
+        : h{c.l.dev.conns,       c.l.dev.listeners_out, c.l.dev.accept_of, c.l.dev.synacks,     c.l.dev.synack_out,
+            c.l.dev.synack_status, c.k.dev.closers_out, c.k.dev.socks_close, c.k.dev.ctl_code, c.o.dev.openers_out,
+            c.o.dev.replies,     c.o.dev.reply_out,     c.o.dev.reply_status} {}
+    template <class T>
+    T* as(rxp::ExtraArray a) const { return static_cast<T*>(d[a]); }
+};
+// The rows e.L lays out, carved from the context's buffer, which has room for them. Those of which the call writes some entries only go in first, so that the whole array comes back with the caller's bytes
+// elsewhere.
+fs_status extra_in(fs_ctx* ctx, RxExtra& e, hipStream_t ks) {
+    for (uint32_t a = 0; a < rxp::kExtraArrays; ++a) {
+        if (!e.h[a] || e.L.room[a] == 0) continue;
+        e.d[a] = ctx->rx_arrays.p + e.L.at[a];
+        if (rxp::kExtraArrayDesc[a].goes_in)
+            FS_HIP_DRAIN(ctx, hipMemcpyAsync(e.d[a], e.h[a], e.L.room[a], hipMemcpyHostToDevice, ks));
+    }
+    return FS_SUCCESS;
+}
+fs_status extra_back(fs_ctx* ctx, const RxExtra& e, hipStream_t ks) {
+    for (uint32_t a = 0; a < rxp::kExtraArrays; ++a)
+        if (e.d[a]) FS_HIP_DRAIN(ctx, hipMemcpyAsync(e.h[a], e.d[a], e.L.room[a], hipMemcpyDeviceToHost, ks));
+    return FS_SUCCESS;
+}
+rxp::ExtraCounts extra_counts(const RxCall& c) {
+    return rxp::ExtraCounts{{c.l.dev.n_slots, c.l.dev.n_listeners, c.k.dev.n_closers, c.s.n_socks, c.o.dev.n_openers, c.b.n}};
+}
+// The three calls' parts as the launches of a host form see them: the counts, and the carved arrays.
+framesum::RxAccept accept_device(const framesum::RxAccept& hx, const RxExtra& e) {
+    return framesum::RxAccept{hx.n_socks, hx.n_listeners, hx.n_slots, hx.synack_flags, e.as<fs_accept_conn>(rxp::kConns),
+                              e.as<fs_listener_out>(rxp::kListenersOut), e.as<uint32_t>(rxp::kAcceptOf),
+                              e.as<uint8_t>(rxp::kSynacks), e.as<fs_digest>(rxp::kSynackOut), e.as<uint8_t>(rxp::kSynackStatus)};
+}
+framesum::RxClose close_device(const framesum::RxClose& hy, const RxExtra& e) {
+    return framesum::RxClose{hy.n_socks, hy.n_closers, e.as<fs_cl_out>(rxp::kClosersOut), e.as<fs_cl_out>(rxp::kSocksClose),
+                             e.as<uint8_t>(rxp::kCtlCode)};
+}
+framesum::RxConnect connect_device(const framesum::RxConnect& hz, const RxExtra& e) {
+    return framesum::RxConnect{hz.n_openers, hz.reply_flags, e.as<fs_cn_out>(rxp::kOpenersOut), e.as<uint8_t>(rxp::kReplies),
+                               e.as<fs_digest>(rxp::kReplyOut), e.as<uint8_t>(rxp::kReplyStatus), e.as<uint8_t>(rxp::kCtlCode)};
 }
 
 // The connect call's host form without a batch: nothing is staged but the openers; the connect stage alone
 // runs on the compute stream over the context's device arrays, and its arrays come back.
 fs_status connect_host_empty(fs_ctx* ctx, const RxCall& c) {
-    const framesum::RxConnect& hz = c.o.z;
-    void* const h_connect[rxp::kConnectArrays] = {hz.openers_out, hz.replies, hz.reply_out, hz.reply_status};
-    const rxp::ConnectLayout NL = rxp::connect_layout(0, hz.n_openers);
+    RxExtra e(c);
+    e.L = rxp::extra_layout(rxp::kConnect, rxp::kConnect, 0, extra_counts(c));
     fs_status st = begin_host_call(ctx);
-    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, NL.bytes);
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, e.L.bytes);
     if (st != FS_SUCCESS) return st;
     const hipStream_t ks = ctx->compute_stream;
     ctx->host_dirty = true;
-    void* d_connect[rxp::kConnectArrays] = {};
-    for (uint32_t a = 0; a < rxp::kConnectArrays; ++a) {
-        if (!h_connect[a] || NL.room[a] == 0) continue;
-        d_connect[a] = ctx->rx_arrays.p + NL.at[a];
-        if (rxp::kConnectArrayDesc[a].goes_in)
-            FS_HIP_DRAIN(ctx, hipMemcpyAsync(d_connect[a], h_connect[a], NL.room[a], hipMemcpyHostToDevice, ks));
-    }
+    st = extra_in(ctx, e, ks);
+    if (st != FS_SUCCESS) return st;
     RxDevice d{c.b, RxResults{}, ks};
-    d.z = connect_device(hz, d_connect, nullptr);
+    d.z = connect_device(c.o.dev, e);
     const RxLaunch how{rx_workgroups(ctx), ctx->flow_hash_mask, ctx->flow_steps, ks};
     RxLeft left{};
     st = connect_stage(ctx, c, d, how, left);
@@ -400,15 +423,15 @@ fs_status connect_host_empty(fs_ctx* ctx, const RxCall& c) {
         drain_host_streams(ctx);
         return st;
     }
-    for (uint32_t a = 0; a < rxp::kConnectArrays; ++a)
-        if (d_connect[a]) FS_HIP_DRAIN(ctx, hipMemcpyAsync(h_connect[a], d_connect[a], NL.room[a], hipMemcpyDeviceToHost, ks));
+    st = extra_back(ctx, e, ks);
+    if (st != FS_SUCCESS) return st;
     FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
     ctx->host_dirty = false;
     return FS_SUCCESS;
 }
 
 // A checked host form: the batch staged through slot 0, the result arrays carved from the context's
-// buffer as plan::rx::layout says, the stages, then what they wrote copied back by the same description.
+// buffer as plan::rx::layout and extra_layout say, the stages, then what they wrote copied back by the same description.
 fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     const RxBatch& b = c.b;
     const RxResults& h = c.r;
@@ -422,28 +445,19 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
         for (uint32_t i = 0; c.kind >= rxp::kRecv && i < s.n_socks; ++i)
             h.snd_out()[i] = rv::untouched(s.snd[i].snd_una, s.snd[i].snd_wnd);
         if (c.kind >= rxp::kAccept) {  // no slot is filled, no listener has a candidate
-            if (c.l.x.n_slots) std::memset(c.l.x.conns, 0, (uint64_t)c.l.x.n_slots * sizeof(fs_accept_conn));
-            if (c.l.x.n_listeners) std::memset(c.l.x.listeners_out, 0, (uint64_t)c.l.x.n_listeners * sizeof(fs_listener_out));
+            if (c.l.dev.n_slots) std::memset(c.l.dev.conns, 0, (uint64_t)c.l.dev.n_slots * sizeof(fs_accept_conn));
+            if (c.l.dev.n_listeners) std::memset(c.l.dev.listeners_out, 0, (uint64_t)c.l.dev.n_listeners * sizeof(fs_listener_out));
         }
         if (c.kind >= rxp::kClose) {  // no connection has a flow
-            for (uint32_t i = 0; i < c.k.y.n_closers; ++i) c.k.y.closers_out[i] = cl::untouched_closer(c.k.closers[i]);
+            for (uint32_t i = 0; i < c.k.dev.n_closers; ++i) c.k.dev.closers_out[i] = cl::untouched_closer(c.k.recs[i]);
             for (uint32_t i = 0; i < s.n_socks; ++i)
-                c.k.y.socks_close[i] = cl::untouched_sock(s.socks[i].rcv_nxt, s.snd[i].snd_una, s.snd[i].snd_wnd, cl::kNone);
+                c.k.dev.socks_close[i] = cl::untouched_sock(s.socks[i].rcv_nxt, s.snd[i].snd_una, s.snd[i].snd_wnd, cl::kNone);
         }
         // no opener has a flow either, yet a flagged one owes its SYN, which only the device builds
-        if (c.kind == rxp::kConnect && c.o.z.n_openers != 0) return connect_host_empty(ctx, c);
+        if (c.kind == rxp::kConnect && c.o.dev.n_openers != 0) return connect_host_empty(ctx, c);
         return FS_SUCCESS;
     }
-    // the accept call's own arrays, as the caller passed them, in plan::rx::AcceptArray's order
-    const bool accepts = c.kind >= rxp::kAccept, closes = c.kind >= rxp::kClose, connects = c.kind == rxp::kConnect;
-    const framesum::RxAccept& hx = c.l.x;
-    void* const h_accept[rxp::kAcceptArrays] = {hx.conns, hx.listeners_out, hx.accept_of, hx.synacks, hx.synack_out, hx.synack_status};
-    // the close call's own arrays likewise, in plan::rx::CloseArray's order
-    const framesum::RxClose& hy = c.k.y;
-    void* const h_close[rxp::kCloseArrays] = {hy.closers_out, hy.socks_close, hy.ctl_code};
-    // the connect call's own arrays likewise, in plan::rx::ConnectArray's order
-    const framesum::RxConnect& hz = c.o.z;
-    void* const h_connect[rxp::kConnectArrays] = {hz.openers_out, hz.replies, hz.reply_out, hz.reply_status};
+    RxExtra e(c);  // the own arrays of the accept, the close and the connect call
     const framesum::plan::Scan sc = framesum::plan::scan_batch(b.offsets, b.lengths, n, frames_bytes);
     if (sc.bad < n) return invalid(ctx, c, "frame " + std::to_string(sc.bad) + " ends past frames_bytes");
     // the device payload buffer: payload_cap, or the most payload the batch can hold when that is less
@@ -451,16 +465,14 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     // the rings' span (the kernels address ring bytes at base + ring_off)
     const uint64_t span = s.span.hi - s.span.lo;
     const rxp::Layout L = rxp::layout(c.kind, n, s.n_socks);
-    const rxp::AcceptLayout AL = rxp::accept_layout(L.bytes, n, hx.n_listeners, hx.n_slots);
-    const rxp::CloseLayout CL = rxp::close_layout(AL.bytes, n, s.n_socks, hy.n_closers);
-    const rxp::ConnectLayout NL = rxp::connect_layout(CL.bytes, hz.n_openers);
+    e.L = rxp::extra_layout(rxp::kAccept, c.kind, L.bytes, extra_counts(c));
     fs_status st = begin_host_call(ctx);
     if (st == FS_SUCCESS && sockets) st = ctx->dl_rings.grow(ctx, span);
     // (the socket calls begin once more, behind the rings' buffer: a second hipSetDevice that keeps their
     // sequence of HIP calls what profiles/rx_call_refactor/calls.txt compares)
     if (st == FS_SUCCESS && sockets) st = begin_host_call(ctx);
     if (st == FS_SUCCESS) st = ctx->co_payload.grow(ctx, d_cap);
-    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, connects ? NL.bytes : closes ? CL.bytes : accepts ? AL.bytes : L.bytes);
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, e.L.bytes);
     if (st != FS_SUCCESS) return st;
     Staged sg;
     st = stage_batch(ctx, b.frames, frames_bytes, sc.lo, sc.hi, b.offsets, b.lengths, n, sg);
@@ -472,35 +484,9 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     for (uint32_t a = 0; a < rxp::kArrays; ++a) d.r.array[a] = h.array[a] && L.has((rxp::Array)a) ? ctx->rx_arrays.p + L.at[a] : nullptr;
     // the span goes in first, so that the copy back returns the caller's own bytes between the rings
     if (span != 0) FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->dl_rings.p, h.rings + s.span.lo, span, hipMemcpyHostToDevice, sg.ks));
-    // the accept call's arrays likewise; those of which the call writes the filled slots' entries only go
-    // in first, so that the whole array comes back with the caller's bytes elsewhere
-    void* d_accept[rxp::kAcceptArrays] = {};
-    for (uint32_t a = 0; accepts && a < rxp::kAcceptArrays; ++a) {
-        if (!h_accept[a] || AL.room[a] == 0) continue;
-        d_accept[a] = ctx->rx_arrays.p + AL.at[a];
-        if (rxp::kAcceptArrayDesc[a].goes_in)
-            FS_HIP_DRAIN(ctx, hipMemcpyAsync(d_accept[a], h_accept[a], AL.room[a], hipMemcpyHostToDevice, sg.ks));
-    }
-    d.x = framesum::RxAccept{hx.n_socks, hx.n_listeners, hx.n_slots, hx.synack_flags,
-                             static_cast<fs_accept_conn*>(d_accept[rxp::kConns]),
-                             static_cast<fs_listener_out*>(d_accept[rxp::kListenersOut]),
-                             static_cast<uint32_t*>(d_accept[rxp::kAcceptOf]),
-                             static_cast<uint8_t*>(d_accept[rxp::kSynacks]),
-                             static_cast<fs_digest*>(d_accept[rxp::kSynackOut]),
-                             static_cast<uint8_t*>(d_accept[rxp::kSynackStatus])};
-    void* d_close[rxp::kCloseArrays] = {};
-    for (uint32_t a = 0; closes && a < rxp::kCloseArrays; ++a)
-        if (h_close[a] && CL.room[a] != 0) d_close[a] = ctx->rx_arrays.p + CL.at[a];
-    d.y = framesum::RxClose{hy.n_socks, hy.n_closers, static_cast<fs_cl_out*>(d_close[rxp::kClosersOut]),
-                            static_cast<fs_cl_out*>(d_close[rxp::kSocksClose]), static_cast<uint8_t*>(d_close[rxp::kCtlCode])};
-    void* d_connect[rxp::kConnectArrays] = {};
-    for (uint32_t a = 0; connects && a < rxp::kConnectArrays; ++a) {
-        if (!h_connect[a] || NL.room[a] == 0) continue;
-        d_connect[a] = ctx->rx_arrays.p + NL.at[a];
-        if (rxp::kConnectArrayDesc[a].goes_in)
-            FS_HIP_DRAIN(ctx, hipMemcpyAsync(d_connect[a], h_connect[a], NL.room[a], hipMemcpyHostToDevice, sg.ks));
-    }
-    d.z = connect_device(hz, d_connect, d.y.ctl_code);
+    st = extra_in(ctx, e, sg.ks);
+    if (st != FS_SUCCESS) return st;
+    d.x = accept_device(c.l.dev, e), d.y = close_device(c.k.dev, e), d.z = connect_device(c.o.dev, e);
     RxLeft left;
     st = rx_run(ctx, c, d, left);
     if (st != FS_SUCCESS) {
@@ -528,12 +514,8 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     FS_HIP_DRAIN(ctx, back(h.payload, ctx->co_payload.p, copied));
     for (uint32_t a = rxp::kTotals + 1; a < rxp::kArrays; ++a)
         FS_HIP_DRAIN(ctx, back(h.array[a], d.r.array[a], rxp::bytes_back(c.kind, (rxp::Array)a, n, s.n_socks, got)));
-    for (uint32_t a = 0; accepts && a < rxp::kAcceptArrays; ++a)
-        FS_HIP_DRAIN(ctx, back(d_accept[a] ? h_accept[a] : nullptr, d_accept[a], AL.room[a]));
-    for (uint32_t a = 0; closes && a < rxp::kCloseArrays; ++a)
-        FS_HIP_DRAIN(ctx, back(d_close[a] ? h_close[a] : nullptr, d_close[a], CL.room[a]));
-    for (uint32_t a = 0; connects && a < rxp::kConnectArrays; ++a)
-        FS_HIP_DRAIN(ctx, back(d_connect[a] ? h_connect[a] : nullptr, d_connect[a], NL.room[a]));
+    st = extra_back(ctx, e, sg.ks);
+    if (st != FS_SUCCESS) return st;
     FS_HIP_DRAIN(ctx, back(s.n_socks ? h.rings + s.span.lo : nullptr, ctx->dl_rings.p, span));
     FS_HIP_DRAIN(ctx, back(h.out, sg.d_out, (uint64_t)n * sizeof(fs_digest)));
     FS_HIP_DRAIN(ctx, back(h.status, sg.d_st, n));

@@ -1,6 +1,6 @@
 // Arithmetic of the close call (fs_close_flows_batch, include/framesum_close.h), free of HIP like
-// framesum_recv.h and framesum_accept.h, on which it builds: the checks of the closer list, the closer
-// table (open addressing over flows::key_hash, built on the host and staged with the records), the rule
+// framesum_recv.h and framesum_accept.h, on which it builds: the checks of the closer list (which build
+// the closer table: flows::build_table, staged with the records), the rule
 // of one frame under one state (code_of, step), what makes a frame an event of the walk, and the out
 // records. framesum_close.hip runs exactly this code per frame, and tests/csrc/test_close.cpp builds it
 // alone under ASan + UBSan.
@@ -33,48 +33,6 @@ enum State : uint32_t {
 // no code of the ABI, the walk ends in front of that frame.
 constexpr uint32_t kCodeData = FS_CL_DATA, kCodeIgnored = FS_CL_IGNORED, kCodeRst = FS_CL_RST, kCodeExpected = FS_CL_EXPECTED;
 constexpr uint32_t kEnds = 0xFFu;
-
-// ---- The closer table: table_slots(n_closers) slots, each a closer's index or kNone, probed as the
-// socket table is (framesum_deliver.h). The result of a lookup does not depend on the hash.
-FS_CO_HD Key closer_key(const fs_cl_sock& s) {
-    Key k;
-    k.w[0] = s.key[0] | ((uint32_t)s.key[1] << 8) | ((uint32_t)s.key[2] << 16) | ((uint32_t)s.key[3] << 24);
-    k.w[1] = s.key[4] | ((uint32_t)s.key[5] << 8) | ((uint32_t)s.key[6] << 16) | ((uint32_t)s.key[7] << 24);
-    k.w[2] = s.key[8] | ((uint32_t)s.key[9] << 8) | ((uint32_t)s.key[10] << 16) | ((uint32_t)s.key[11] << 24);
-    k.w[3] = s.key[12] | kKeyAccepted;
-    return k;
-}
-// The closer whose key equals `key`, or kNone. At most every slot once.
-FS_CO_HD uint32_t lookup_closer(const Key& key, const fs_cl_sock* closers, const uint32_t* table, uint32_t tmask,
-                                uint32_t hash_mask) {
-    uint32_t s = table_start(key, hash_mask, tmask);
-    for (uint32_t probe = 0; probe <= tmask; ++probe) {
-        const uint32_t owner = table[s];
-        if (owner == kNone) return kNone;
-        if (same_key(key, closer_key(closers[owner]))) return owner;
-        s = (s + 1u) & tmask;
-    }
-    return kNone;
-}
-// Fills `table` (table_slots(n_closers) entries). Returns kNone, or the first closer whose key an
-// earlier closer has already.
-inline uint32_t build_closer_table(const fs_cl_sock* closers, uint32_t n_closers, uint32_t hash_mask, uint32_t* table) {
-    const uint32_t slots = table_slots(n_closers), tmask = slots - 1u;
-    for (uint32_t i = 0; i < slots; ++i) table[i] = kNone;
-    for (uint32_t i = 0; i < n_closers; ++i) {
-        const Key key = closer_key(closers[i]);
-        uint32_t s = table_start(key, hash_mask, tmask);
-        for (uint32_t probe = 0; probe <= tmask; ++probe) {
-            if (table[s] == kNone) {
-                table[s] = i;
-                break;
-            }
-            if (same_key(key, closer_key(closers[table[s]]))) return i;
-            s = (s + 1u) & tmask;
-        }
-    }
-    return kNone;
-}
 
 // ---- The checks of the closer list (rule 7 of the header), none of which needs a device.
 enum BadClose {
@@ -114,10 +72,10 @@ inline CheckClose check_closers(const fs_cl_sock* closers, uint32_t n_closers, b
         if (c.snd_wnd > kMaxWnd) return CheckClose{kCloseSndWnd, i};
     }
     table.resize(table_slots(n_closers));
-    const uint32_t dup = build_closer_table(closers, n_closers, hash_mask, table.data());
+    const uint32_t dup = build_table(closers, n_closers, hash_mask, table.data());
     if (dup != kNone) return CheckClose{kCloseEqualKeys, dup};
     for (uint32_t i = 0; n_socks != 0 && i < n_closers; ++i)
-        if (lookup(closer_key(closers[i]), socks, sock_table, table_slots(n_socks) - 1u, hash_mask) != kNone)
+        if (lookup(wire_key(closers[i].key), socks, sock_table, table_slots(n_socks) - 1u, hash_mask) != kNone)
             return CheckClose{kCloseKeyListed, i};
     return CheckClose{kCloseGood, 0u};
 }

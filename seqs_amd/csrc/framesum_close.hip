@@ -10,10 +10,11 @@
 // The launches on the caller's stream, none of which waits on another workgroup or wave of its own
 // launch, every loop bounded by a count known at its start:
 //   (memset)  `ctl_code` to 0, the closers' first slots to "none".
-//   mark      one lane per slot that opens a flow: the probe of the staged closer table (at most every
-//             table slot once); the flow's closer, the closer's first slot.
-//   gather    one lane per slot of a closer's flow: Seq, Ack, the dword at L4 + 12 and the payload length
-//             into per-slot scratch, so that the walk's loads are contiguous. (The slots of a listed
+//   match     flow_match (framesum_match_dev.h) over the staged closer table: the flow's closer, the
+//             closer's first slot.
+//   gather    flow_gather_sq, which the connect call launches too: one lane per slot of a closer's flow:
+//             Seq, Ack, the dword at L4 + 12 and the payload length into per-slot scratch, so that the
+//             walk's loads are contiguous. (The slots of a listed
 //             socket's flow need none: the delivery's mark and the receive call's gather have left all
 //             four values for every slot of such a flow, also behind `stop`.)
 //   walk      one wave per closer and one per listed socket: the flow's slots in chunks of 64, the next
@@ -31,6 +32,7 @@
 #include "framesum_coalesce_dev.h"
 #include "framesum_flows.h"
 #include "framesum_internal.h"
+#include "framesum_match_dev.h"
 
 namespace framesum {
 
@@ -39,7 +41,8 @@ namespace {
 using namespace codev;
 namespace cl = closing;
 
-struct ClArgs : FlowView {  // (the flow launches' scratch of this call)
+// (the match's record in front: the owners are the closers)
+struct ClArgs : FlowMatch<fs_cl_sock> {
     const uint8_t* frames;
     const uint64_t* offsets;
     const fs_rx_flow_totals* totals;
@@ -49,46 +52,33 @@ struct ClArgs : FlowView {  // (the flow launches' scratch of this call)
     const uint32_t* sock_first;
     const fs_rx_sock_out* socks_out;
     const fs_rx_snd_out* snd_out;
-    // the staged block
-    const fs_cl_sock* closers;
-    const uint32_t* table;
+    // the staged block, behind the closers and their table
     const cl::Fixed* socks;  // per listed socket
     // this call's own scratch
-    uint32_t* flow_closer;   // per flow: its closer, or none
-    uint32_t* closer_first;  // per closer: its flow's first slot, or none
-    uint4* sq;               // per slot of a closer's flow: Seq, Ack, the dword at L4 + 12, the payload length
+    const uint4* sq;  // per slot of a closer's flow: Seq, Ack, the dword at L4 + 12, the payload length
     // the results
     fs_cl_out* closers_out;
     fs_cl_out* socks_close;
     uint8_t* ctl_code;
-    uint32_t n, n_blocks, n_socks, n_closers, tmask, hash_mask;
+    uint32_t n_socks;
 };
 
-__global__ void __launch_bounds__(kThreads) close_mark(const ClArgs a) {
-    for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
-        const uint32_t k = blk * kScanBlock + threadIdx.x;
-        if (k >= a.n) continue;
-        const uint32_t y = a.rec[k].y;
-        if (!(y & kAccepted) || !(y & flows::kFlowHead)) continue;
-        const uint32_t f = a.flowidx[k];
-        if (f >= a.n) continue;  // (the flow launches rule this out)
-        const uint4 v = a.keys[slot_frame(a, k)];
-        const flows::Key key{{v.x, v.y, v.z, v.w}};
-        uint32_t c = cl::kNone;
-        if (flows::key_byte(key, 0) == 6u) c = cl::lookup_closer(key, a.closers, a.table, a.tmask, a.hash_mask);
-        a.flow_closer[f] = c;
-        if (c < a.n_closers) a.closer_first[c] = k;  // (distinct keys on both sides: one flow per closer)
-    }
-}
-
-__global__ void __launch_bounds__(kThreads) close_gather(const ClArgs a) {
+// The gather of the close and of the connect call: one lane per slot of an owner's flow.
+struct SqArgs : FlowView {
+    const uint8_t* frames;
+    const uint64_t* offsets;
+    const uint32_t* flow_owner;
+    uint4* sq;
+    uint32_t n, n_blocks, n_owners;
+};
+__global__ void __launch_bounds__(kThreads) flow_gather_sq(const SqArgs a) {
     for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
         const uint32_t k = blk * kScanBlock + threadIdx.x;
         if (k >= a.n) continue;
         const uint2 r = a.rec[k];
         if (!(r.y & kAccepted)) continue;
         const uint32_t f = a.flowidx[k];
-        if (f >= a.n || a.flow_closer[f] >= a.n_closers) continue;
+        if (f >= a.n || a.flow_owner[f] >= a.n_owners) continue;
         // an accepted TCP frame holds its whole TCP header (the verdict's gates)
         const uint8_t* __restrict__ p = a.frames + a.offsets[slot_frame(a, k)];
         const uint32_t l4 = 14u + 4u * (p[14] & 15u);
@@ -108,17 +98,16 @@ __device__ __forceinline__ Held hold(const ClArgs& a, bool from_sock, uint32_t f
     Held h{0u, 0u, cl::Seg{0u, 0u, 0u, 0u, 0u}};
     if (k < n_acc) {
         const uint32_t y = a.rec[k].y;
-        uint32_t seq, ack, dword12, len;
+        uint4 q;
         if (from_sock) {
             const uint2 m = a.mk[k], w = a.aw[k];
-            seq = m.x, len = m.y & 0xFFFFu, ack = w.x, dword12 = w.y;
+            q = make_uint4(m.x, w.x, w.y, m.y & 0xFFFFu);
         } else {
-            const uint4 q = a.sq[k];
-            seq = q.x, ack = q.y, dword12 = q.z, len = q.w;
+            q = a.sq[k];
         }
         h.frame = slot_frame(a, k);
         h.in = (k == first || !(y & flows::kFlowHead)) ? 1u : 0u;
-        h.f = cl::Seg{seq, ack, recv::window_of(dword12), recv::flags9_of(dword12), len};
+        h.f = seg_of(q);
     }
     return h;
 }
@@ -127,10 +116,6 @@ __device__ __forceinline__ unsigned long long lanes_from_to(uint32_t lo, uint32_
     const unsigned long long below_hi = hi >= 64u ? ~0ull : (1ull << hi) - 1ull;
     const unsigned long long below_lo = lo >= 64u ? ~0ull : (1ull << lo) - 1ull;
     return below_hi & ~below_lo;
-}
-__device__ __forceinline__ cl::Seg lane_seg(const cl::Seg& f, uint32_t l) {
-    return cl::Seg{lane_value(f.seq, l), lane_value(f.ack, l), lane_value(f.window, l), lane_value(f.flags9, l),
-                   lane_value(f.len, l)};
 }
 
 // The walk's state between chunks, the same in all lanes.
@@ -205,12 +190,12 @@ __device__ __forceinline__ void walk_flow(const ClArgs& a, const cl::Fixed& x, b
 
 __global__ void __launch_bounds__(kThreads) close_walk(const ClArgs a) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t n_walks = a.n_closers + a.n_socks;
+    const uint32_t n_walks = a.n_owners + a.n_socks;
     for (uint32_t i = blockIdx.x * kWaves + wave; i < n_walks; i += gridDim.x * kWaves) {
-        if (i < a.n_closers) {
-            const fs_cl_sock sk = a.closers[i];
+        if (i < a.n_owners) {
+            const fs_cl_sock sk = a.recs[i];
             fs_cl_out o = cl::untouched_closer(sk);
-            const uint32_t first = a.closer_first[i];
+            const uint32_t first = a.owner_first[i];
             if (first < a.n) {
                 Walk w{cl::ctl_of(sk), 0u, 0u, first};
                 walk_flow(a, cl::Fixed{sk.snd_nxt, sk.rcv_wnd}, false, first, first, lane, w);
@@ -220,7 +205,7 @@ __global__ void __launch_bounds__(kThreads) close_walk(const ClArgs a) {
             continue;
         }
         // an Established socket: where the receive call's walk ended
-        const uint32_t s = i - a.n_closers;
+        const uint32_t s = i - a.n_owners;
         const cl::Fixed x = a.socks[s];
         const fs_rx_sock_out so = a.socks_out[s];
         const fs_rx_snd_out sn = a.snd_out[s];
@@ -258,25 +243,43 @@ __global__ void __launch_bounds__(kThreads) close_walk(const ClArgs a) {
 
 }  // namespace
 
-CloseScratch close_scratch(uint32_t n, uint32_t n_closers) {
-    CloseScratch s;
+OwnerScratch owner_scratch(uint32_t n, uint32_t n_owners) {
+    OwnerScratch s;
     uint64_t at = 0;
     s.sq = at, at += 16ull * n;
-    s.flow_closer = at, at += 4ull * n;
-    s.closer_first = at, at += 4ull * n_closers;
+    s.flow_owner = at, at += 4ull * n;
+    s.owner_first = at, at += 4ull * n_owners;
     s.bytes = at;
     return s;
+}
+
+void launch_flow_gather_sq(const RxBatch& b, const RxLeft& left, uint8_t* scratch, const OwnerScratch& s, uint32_t n_owners,
+                           const RxLaunch& how) {
+    const ScanGrid g = scan_grid(b.n, how);
+    SqArgs a;
+    static_cast<FlowView&>(a) = flow_view(left, b.n);
+    a.frames = b.frames;
+    a.offsets = b.offsets;
+    a.flow_owner = reinterpret_cast<const uint32_t*>(scratch + s.flow_owner);
+    a.sq = reinterpret_cast<uint4*>(scratch + s.sq);
+    a.n = b.n;
+    a.n_blocks = g.blocks;
+    a.n_owners = n_owners;
+    hipLaunchKernelGGL(flow_gather_sq, dim3(g.scan), dim3(kThreads), 0, how.stream, a);
 }
 
 hipError_t launch_close(const RxBatch& b, const RxResults& r, const RxClose& y, const RxLeft& left, const uint8_t* d_block,
                         const RxLaunch& how) {
     uint8_t* const scratch = left.close_scratch;
-    const CloseScratch& s = left.cs;
+    const OwnerScratch& s = left.cs;
     const uint32_t n = b.n;
     const hipStream_t stream = how.stream;
     const bool socks = y.n_socks != 0;
+    const ScanGrid g = scan_grid(n, how);
+    const closing::Block blk = closing::block_of(y.n_closers, y.n_socks);
     ClArgs a;
-    static_cast<FlowView&>(a) = flow_view(left, n);
+    fill_match(a, flow_view(left, n), d_block, blk.table, reinterpret_cast<uint32_t*>(scratch + s.flow_owner),
+               reinterpret_cast<uint32_t*>(scratch + s.owner_first), n, y.n_closers, how);
     a.frames = b.frames;
     a.offsets = b.offsets;
     a.totals = static_cast<const fs_rx_flow_totals*>(r.totals());
@@ -285,34 +288,22 @@ hipError_t launch_close(const RxBatch& b, const RxResults& r, const RxClose& y, 
     a.sock_first = socks ? reinterpret_cast<const uint32_t*>(left.deliver_scratch + left.ds.sock_first) : nullptr;
     a.socks_out = r.socks_out();
     a.snd_out = r.snd_out();
-    a.closers = reinterpret_cast<const fs_cl_sock*>(d_block);
-    const closing::Block blk = closing::block_of(y.n_closers, y.n_socks);
-    a.table = reinterpret_cast<const uint32_t*>(d_block + blk.table);
     a.socks = reinterpret_cast<const cl::Fixed*>(d_block + blk.socks);
-    a.flow_closer = reinterpret_cast<uint32_t*>(scratch + s.flow_closer);
-    a.closer_first = reinterpret_cast<uint32_t*>(scratch + s.closer_first);
-    a.sq = reinterpret_cast<uint4*>(scratch + s.sq);
+    a.sq = reinterpret_cast<const uint4*>(scratch + s.sq);
     a.closers_out = y.closers_out;
     a.socks_close = y.socks_close;
     a.ctl_code = y.ctl_code;
-    a.n = n;
-    a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
     a.n_socks = y.n_socks;
-    a.n_closers = y.n_closers;
-    a.tmask = flows::table_slots(y.n_closers) - 1u;
-    a.hash_mask = how.hash_mask;
-    const uint32_t cap = (uint32_t)(how.max_workgroups > 0 ? how.max_workgroups : 1);
-    const uint32_t scan_grid = a.n_blocks < cap ? a.n_blocks : cap;
     const uint32_t walk_blocks = (y.n_closers + y.n_socks + kWaves - 1u) / kWaves;
     if (y.n_closers != 0) {
-        const hipError_t e = hipMemsetAsync(a.closer_first, 0xFF, 4ull * y.n_closers, stream);
+        const hipError_t e = hipMemsetAsync(a.owner_first, 0xFF, 4ull * y.n_closers, stream);
         if (e != hipSuccess) return e;
         if (n != 0) {
-            hipLaunchKernelGGL(close_mark, dim3(scan_grid), dim3(kThreads), 0, stream, a);
-            hipLaunchKernelGGL(close_gather, dim3(scan_grid), dim3(kThreads), 0, stream, a);
+            hipLaunchKernelGGL(flow_match<fs_cl_sock>, dim3(g.scan), dim3(kThreads), 0, stream, a);
+            launch_flow_gather_sq(b, left, scratch, s, y.n_closers, how);
         }
     }
-    hipLaunchKernelGGL(close_walk, dim3(walk_blocks < cap ? walk_blocks : cap), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(close_walk, dim3(g.capped(walk_blocks)), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -299,6 +299,17 @@ __device__ __forceinline__ void gather_copy(const A& a) {
 struct GatherGrids {
     uint32_t scan, copy;
 };
+// The same for any launch of a call over n slots: `blocks` blocks of kScanBlock slots (a kernel's
+// n_blocks) run by `scan` workgroups; capped(want) for a kernel that wants another count.
+struct ScanGrid {
+    uint32_t blocks, scan, cap;
+    uint32_t capped(uint32_t want) const { return want < cap ? want : cap; }
+};
+inline ScanGrid scan_grid(uint32_t n, const RxLaunch& how) {
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
+    const uint32_t cap = (uint32_t)(how.max_workgroups > 0 ? how.max_workgroups : 1);
+    return ScanGrid{blocks, blocks < cap ? blocks : cap, cap};
+}
 template <typename A, typename S>
 GatherGrids fill_gather_args(A& a, const RxBatch& b, const RxResults& r, uint8_t* scratch, const S& s, int max_workgroups) {
     const uint32_t n = b.n;

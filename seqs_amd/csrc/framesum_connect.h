@@ -1,6 +1,6 @@
 // Arithmetic of the connect call (fs_connect_flows_batch, include/framesum_connect.h), free of HIP like
-// framesum_close.h, on which it builds: the checks of the opener list, the opener table (open addressing
-// over flows::key_hash, built on the host and staged with the records), the rule of one frame of an
+// framesum_close.h, on which it builds: the checks of the opener list (which build the opener
+// table: flows::build_table, staged with the records), the rule of one frame of an
 // opener's flow (code_of), the event that ends a walk (apply), the reply's header template, and the out
 // record. framesum_connect.hip runs exactly this code per frame, and tests/csrc/test_connect.cpp builds
 // it alone under ASan + UBSan.
@@ -33,48 +33,6 @@ constexpr uint32_t kSynRcvd = FS_ST_SYN_RCVD, kSynSent = FS_ST_SYN_SENT, kEstabl
 constexpr uint32_t kCodeExpected = FS_CL_EXPECTED, kCodeBadAck = FS_CN_BAD_ACK;
 constexpr uint32_t kEndsRst = 0xFEu, kEndsSyn = 0xFFu;
 constexpr uint32_t kOpenWnd = 1u;  // snd.WND of a block Open has made (control_user.go:64)
-
-// ---- The opener table: table_slots(n_openers) slots, each an opener's index or kNone, probed as the
-// closer table is (framesum_close.h). The result of a lookup does not depend on the hash.
-FS_CO_HD Key opener_key(const fs_cn_sock& s) {
-    Key k;
-    k.w[0] = s.key[0] | ((uint32_t)s.key[1] << 8) | ((uint32_t)s.key[2] << 16) | ((uint32_t)s.key[3] << 24);
-    k.w[1] = s.key[4] | ((uint32_t)s.key[5] << 8) | ((uint32_t)s.key[6] << 16) | ((uint32_t)s.key[7] << 24);
-    k.w[2] = s.key[8] | ((uint32_t)s.key[9] << 8) | ((uint32_t)s.key[10] << 16) | ((uint32_t)s.key[11] << 24);
-    k.w[3] = s.key[12] | kKeyAccepted;
-    return k;
-}
-// The opener whose key equals `key`, or kNone. At most every slot once.
-FS_CO_HD uint32_t lookup_opener(const Key& key, const fs_cn_sock* openers, const uint32_t* table, uint32_t tmask,
-                                uint32_t hash_mask) {
-    uint32_t s = table_start(key, hash_mask, tmask);
-    for (uint32_t probe = 0; probe <= tmask; ++probe) {
-        const uint32_t owner = table[s];
-        if (owner == kNone) return kNone;
-        if (same_key(key, opener_key(openers[owner]))) return owner;
-        s = (s + 1u) & tmask;
-    }
-    return kNone;
-}
-// Fills `table` (table_slots(n_openers) entries). Returns kNone, or the first opener whose key an
-// earlier opener has already.
-inline uint32_t build_opener_table(const fs_cn_sock* openers, uint32_t n_openers, uint32_t hash_mask, uint32_t* table) {
-    const uint32_t slots = table_slots(n_openers), tmask = slots - 1u;
-    for (uint32_t i = 0; i < slots; ++i) table[i] = kNone;
-    for (uint32_t i = 0; i < n_openers; ++i) {
-        const Key key = opener_key(openers[i]);
-        uint32_t s = table_start(key, hash_mask, tmask);
-        for (uint32_t probe = 0; probe <= tmask; ++probe) {
-            if (table[s] == kNone) {
-                table[s] = i;
-                break;
-            }
-            if (same_key(key, opener_key(openers[table[s]]))) return i;
-            s = (s + 1u) & tmask;
-        }
-    }
-    return kNone;
-}
 
 // ---- The checks of the opener list (section 6 of the header), none of which needs a device.
 enum BadConnect {
@@ -116,14 +74,13 @@ inline CheckConnect check_openers(const fs_cn_sock* openers, uint32_t n_openers,
         if (c.reserved[0] | c.reserved[1] | c.reserved2) return CheckConnect{kConnectReserved, i};
     }
     table.resize(table_slots(n_openers));
-    const uint32_t dup = build_opener_table(openers, n_openers, hash_mask, table.data());
+    const uint32_t dup = build_table(openers, n_openers, hash_mask, table.data());
     if (dup != kNone) return CheckConnect{kConnectEqualKeys, dup};
     for (uint32_t i = 0; i < n_openers; ++i) {
-        const Key key = opener_key(openers[i]);
+        const Key key = wire_key(openers[i].key);
         if (n_socks != 0 && lookup(key, socks, sock_table, table_slots(n_socks) - 1u, hash_mask) != kNone)
             return CheckConnect{kConnectKeyListed, i};
-        if (n_closers != 0 &&
-            closing::lookup_closer(key, closers, closer_table, table_slots(n_closers) - 1u, hash_mask) != kNone)
+        if (n_closers != 0 && lookup(key, closers, closer_table, table_slots(n_closers) - 1u, hash_mask) != kNone)
             return CheckConnect{kConnectKeyCloser, i};
     }
     return CheckConnect{kConnectGood, 0u};

@@ -1,6 +1,6 @@
 // Arithmetic of the in-order TCP delivery (fs_deliver_flows_batch, include/framesum_deliver.h), free
-// of HIP like framesum_flows.h, on which it builds: the checks of the socket list, the socket table
-// (open addressing over flows::key_hash, built on the host and staged with the records), the
+// of HIP like framesum_flows.h, on which it builds: the checks of the socket list (which build the
+// socket table: flows::build_table, staged with the records), the
 // admission rule of one segment and the split of a ring write at the wrap. framesum_deliver.hip runs
 // exactly this code per frame, and tests/csrc/test_deliver.cpp builds it alone under ASan + UBSan.
 #pragma once
@@ -25,53 +25,7 @@ constexpr uint32_t kAck = 0x10;
 
 static_assert(sizeof(fs_rx_sock) == 48 && sizeof(fs_rx_sock_out) == 32, "fs_rx_sock / fs_rx_sock_out layout");
 
-// A socket's key as the key record of its frames (framesum_flows.h): same_key() compares the two.
-FS_CO_HD Key sock_key(const fs_rx_sock& s) {
-    Key k;
-    k.w[0] = s.key[0] | ((uint32_t)s.key[1] << 8) | ((uint32_t)s.key[2] << 16) | ((uint32_t)s.key[3] << 24);
-    k.w[1] = s.key[4] | ((uint32_t)s.key[5] << 8) | ((uint32_t)s.key[6] << 16) | ((uint32_t)s.key[7] << 24);
-    k.w[2] = s.key[8] | ((uint32_t)s.key[9] << 8) | ((uint32_t)s.key[10] << 16) | ((uint32_t)s.key[11] << 24);
-    k.w[3] = s.key[12] | kKeyAccepted;
-    return k;
-}
-
-// ---- The socket table: table_slots(n_socks) slots (a power of two of at least 2 n_socks, so at most
-// half full), each a socket's index or kNone; a key starts probing at its hash & hash_mask (all ones
-// in the product) and goes on linearly.
-FS_CO_HD uint32_t table_start(const Key& k, uint32_t hash_mask, uint32_t tmask) { return key_hash(k) & hash_mask & tmask; }
-
-// The socket whose key equals `key`, or kNone. At most every slot once.
-FS_CO_HD uint32_t lookup(const Key& key, const fs_rx_sock* socks, const uint32_t* table, uint32_t tmask,
-                         uint32_t hash_mask) {
-    uint32_t s = table_start(key, hash_mask, tmask);
-    for (uint32_t probe = 0; probe <= tmask; ++probe) {
-        const uint32_t owner = table[s];
-        if (owner == kNone) return kNone;
-        if (same_key(key, sock_key(socks[owner]))) return owner;
-        s = (s + 1u) & tmask;
-    }
-    return kNone;
-}
-
-// Fills `table` (table_slots(n_socks) entries). Returns kNone, or the first socket whose key an
-// earlier socket has already.
-inline uint32_t build_table(const fs_rx_sock* socks, uint32_t n_socks, uint32_t hash_mask, uint32_t* table) {
-    const uint32_t slots = table_slots(n_socks), tmask = slots - 1u;
-    for (uint32_t i = 0; i < slots; ++i) table[i] = kNone;
-    for (uint32_t i = 0; i < n_socks; ++i) {
-        const Key key = sock_key(socks[i]);
-        uint32_t s = table_start(key, hash_mask, tmask);
-        for (uint32_t probe = 0; probe <= tmask; ++probe) {
-            if (table[s] == kNone) {
-                table[s] = i;
-                break;
-            }
-            if (same_key(key, sock_key(socks[table[s]]))) return i;
-            s = (s + 1u) & tmask;
-        }
-    }
-    return kNone;
-}
+static_assert(kNone == kEmpty, "the socket table's empty slot (framesum_flows.h) is the ABI's \"none\"");
 
 // ---- The checks of the socket list, none of which needs a device.
 enum Bad {

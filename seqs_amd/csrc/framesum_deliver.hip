@@ -7,9 +7,8 @@
 // The launches on the caller's stream, none of which waits on another workgroup or wave of its own
 // launch, every loop bounded by a count known at its start:
 //   (memset)  the per-slot ring positions and the per-socket first slots to "none", `delivered` to 0.
-//   match     one lane per slot that opens a flow: probe the staged socket table with the key record
-//             of the slot's frame (at most every table slot once); the flow's socket, the socket's
-//             first slot.
+//   match     flow_match (framesum_match_dev.h) over the staged socket table: the flow's socket, the
+//             socket's first slot.
 //   mark      one lane per slot of a matched flow: Seq and Ack from the frame at L4 = 14 + 4 IHL, and
 //             the bits of the rule that do not depend on the frames before: considered, window and
 //             ACK check, SYN | RST, FIN (framesum_deliver.h mark_word).
@@ -31,6 +30,7 @@
 #include "framesum_deliver.h"
 #include "framesum_flows.h"
 #include "framesum_internal.h"
+#include "framesum_match_dev.h"
 
 namespace framesum {
 
@@ -39,40 +39,20 @@ namespace {
 using namespace codev;
 namespace dl = deliver;
 
-struct DlArgs : FlowView {  // (the flow launches' scratch of this call)
+// (the match's record in front: the owners are the listed sockets)
+struct DlArgs : FlowMatch<fs_rx_sock> {
     const uint8_t* frames;
     const uint64_t* offsets;
     const fs_rx_flow_totals* totals;
-    // the staged block
-    const fs_rx_sock* socks;
-    const uint32_t* table;
     // this call's own scratch
-    uint32_t* flow_sock;   // per flow: its socket, or none
-    uint2* mk;             // per slot of a matched flow: Seq, mark_word
-    uint32_t* dwpos;       // per slot: where in its socket's ring the payload goes, or none
-    uint32_t* sock_first;  // per socket: its flow's first slot, or none
+    uint2* mk;        // per slot of a matched flow: Seq, mark_word
+    uint32_t* dwpos;  // per slot: where in its socket's ring the payload goes, or none
     uint8_t* rings;
     fs_rx_sock_out* socks_out;
     uint8_t* delivered;
-    uint32_t n, n_blocks, n_socks, tmask, hash_mask;
 };
 
 __device__ __forceinline__ uint32_t be32_at(const uint8_t* p) { return __builtin_bswap32(load_at<uint32_t>(p)); }
-
-__global__ void __launch_bounds__(kThreads) deliver_match(const DlArgs a) {
-    for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
-        const uint32_t k = blk * kScanBlock + threadIdx.x;
-        if (k >= a.n) continue;
-        const uint32_t y = a.rec[k].y;
-        if (!(y & kAccepted) || !(y & flows::kFlowHead)) continue;
-        const uint4 v = a.keys[slot_frame(a, k)];
-        const flows::Key key{{v.x, v.y, v.z, v.w}};
-        uint32_t s = dl::kNone;
-        if (flows::key_byte(key, 0) == 6u) s = dl::lookup(key, a.socks, a.table, a.tmask, a.hash_mask);
-        a.flow_sock[a.flowidx[k]] = s;
-        if (s < a.n_socks) a.sock_first[s] = k;  // (distinct keys on both sides: one flow per socket)
-    }
-}
 
 __global__ void __launch_bounds__(kThreads) deliver_mark(const DlArgs a) {
     for (uint32_t blk = blockIdx.x; blk < a.n_blocks; blk += gridDim.x) {
@@ -80,13 +60,13 @@ __global__ void __launch_bounds__(kThreads) deliver_mark(const DlArgs a) {
         if (k >= a.n) continue;
         const uint2 r = a.rec[k];
         if (!(r.y & kAccepted)) continue;
-        const uint32_t s = a.flow_sock[a.flowidx[k]];
-        if (s >= a.n_socks) continue;
+        const uint32_t s = a.flow_owner[a.flowidx[k]];
+        if (s >= a.n_owners) continue;
         // an accepted TCP frame holds its whole TCP header (the verdict's gates)
         const uint8_t* __restrict__ p = a.frames + a.offsets[slot_frame(a, k)];
         const uint32_t l4 = 14u + 4u * (p[14] & 15u);
         const uint32_t seq = be32_at(p + l4 + 4u), ack = be32_at(p + l4 + 8u);
-        a.mk[k] = make_uint2(seq, dl::mark_word(rec_len(r.x), rec_flags(r.x), ack, a.socks[s].rcv_wnd, a.socks[s].snd_nxt));
+        a.mk[k] = make_uint2(seq, dl::mark_word(rec_len(r.x), rec_flags(r.x), ack, a.recs[s].rcv_wnd, a.recs[s].snd_nxt));
     }
 }
 
@@ -198,10 +178,10 @@ constexpr uint32_t kAhead = 4;
 __global__ void __launch_bounds__(kThreads) deliver_walk(const DlArgs a) {
     __shared__ WaveScan::storage_type s_scan[kWaves];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t s = blockIdx.x * kWaves + wave; s < a.n_socks; s += gridDim.x * kWaves) {
-        const fs_rx_sock sk = a.socks[s];
+    for (uint32_t s = blockIdx.x * kWaves + wave; s < a.n_owners; s += gridDim.x * kWaves) {
+        const fs_rx_sock sk = a.recs[s];
         fs_rx_sock_out o = dl::untouched(sk);
-        const uint32_t first = a.sock_first[s];
+        const uint32_t first = a.owner_first[s];
         if (first < a.n) {
             const uint32_t n_acc = a.totals->n_accepted < a.n ? a.totals->n_accepted : a.n;
             dl::State st{sk.rcv_nxt, sk.ring_wpos, sk.ring_free};
@@ -236,10 +216,10 @@ __global__ void __launch_bounds__(kThreads) deliver_copy(const DlArgs a) {
         const uint32_t pos = a.dwpos[k];
         if (pos == dl::kNone) continue;
         const uint32_t x = a.rec[k].x, len = rec_len(x);
-        const uint32_t s = a.flow_sock[a.flowidx[k]];
-        if (len == 0 || s >= a.n_socks) continue;  // (an admitted FIN without data)
-        const uint64_t ring_off = a.socks[s].ring_off;
-        const uint32_t size = a.socks[s].ring_size;
+        const uint32_t s = a.flow_owner[a.flowidx[k]];
+        if (len == 0 || s >= a.n_owners) continue;  // (an admitted FIN without data)
+        const uint64_t ring_off = a.recs[s].ring_off;
+        const uint32_t size = a.recs[s].ring_size;
         if (pos >= size || len > size) continue;  // (the walk rules this out)
         const uint8_t* src = a.frames + a.offsets[slot_frame(a, k)] + rec_start(x);
         uint8_t* ring = a.rings + ring_off;
@@ -268,36 +248,28 @@ hipError_t launch_deliver(const RxBatch& b, const RxResults& r, const RxLeft& le
     const DeliverScratch& s = left.ds;
     const uint32_t n = b.n;
     const hipStream_t stream = how.stream;
+    const ScanGrid g = scan_grid(n, how);
     DlArgs a;
-    static_cast<FlowView&>(a) = flow_view(left, n);
+    fill_match(a, flow_view(left, n), d_block, dl::block_of(n_socks).table, reinterpret_cast<uint32_t*>(scratch + s.flow_sock),
+               reinterpret_cast<uint32_t*>(scratch + s.sock_first), n, n_socks, how);
     a.frames = b.frames;
     a.offsets = b.offsets;
     a.totals = static_cast<const fs_rx_flow_totals*>(r.totals());
-    a.socks = reinterpret_cast<const fs_rx_sock*>(d_block);
-    a.table = reinterpret_cast<const uint32_t*>(d_block + dl::block_of(n_socks).table);
-    a.flow_sock = reinterpret_cast<uint32_t*>(scratch + s.flow_sock);
     a.mk = reinterpret_cast<uint2*>(scratch + s.mk);
     a.dwpos = reinterpret_cast<uint32_t*>(scratch + s.dwpos);
-    a.sock_first = reinterpret_cast<uint32_t*>(scratch + s.sock_first);
     a.rings = r.rings;
     a.socks_out = r.socks_out();
     a.delivered = r.delivered();
-    a.n = n;
-    a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
-    a.n_socks = n_socks;
-    a.tmask = flows::table_slots(n_socks) - 1u;
-    a.hash_mask = how.hash_mask;
-    const uint32_t cap = (uint32_t)(how.max_workgroups > 0 ? how.max_workgroups : 1);
     const uint32_t n_tiles = (uint32_t)(((uint64_t)n + kTileFrames - 1) / kTileFrames);
     const uint32_t walk_blocks = (n_socks + kWaves - 1u) / kWaves;
     hipError_t e = hipMemsetAsync(scratch + s.dwpos, 0xFF, 4ull * n + 4ull * n_socks, stream);
     if (e != hipSuccess) return e;
     if (n != 0) {
-        hipLaunchKernelGGL(deliver_match, dim3(a.n_blocks < cap ? a.n_blocks : cap), dim3(kThreads), 0, stream, a);
-        hipLaunchKernelGGL(deliver_mark, dim3(a.n_blocks < cap ? a.n_blocks : cap), dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(flow_match<fs_rx_sock>, dim3(g.scan), dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(deliver_mark, dim3(g.scan), dim3(kThreads), 0, stream, a);
     }
-    hipLaunchKernelGGL(deliver_walk, dim3(walk_blocks < cap ? walk_blocks : cap), dim3(kThreads), 0, stream, a);
-    if (n != 0) hipLaunchKernelGGL(deliver_copy, dim3(n_tiles < cap ? n_tiles : cap), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(deliver_walk, dim3(g.capped(walk_blocks)), dim3(kThreads), 0, stream, a);
+    if (n != 0) hipLaunchKernelGGL(deliver_copy, dim3(g.capped(n_tiles)), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 

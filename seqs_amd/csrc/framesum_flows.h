@@ -1,8 +1,10 @@
 // Arithmetic of the flow-aware RX coalesce (fs_coalesce_flows_batch), free of HIP like
 // framesum_coalesce.h, on which it builds: a frame's 13-byte flow key, key equality and hash, the
-// flow table's size and the 64-bit sort key that puts the accepted frames into delivery order.
-// framesum_flows.hip runs exactly this code per frame, and tests/csrc/test_flows.cpp builds it alone
-// under ASan + UBSan.
+// flow table's size and the 64-bit sort key that puts the accepted frames into delivery order; and the
+// keyed table of a connection list, which the calls behind the flow launches build and probe
+// (framesum_deliver.h, framesum_close.h, framesum_connect.h and their kernels). framesum_flows.hip runs
+// exactly this code per frame, and tests/csrc/test_flows.cpp and test_deliver.cpp build it alone under
+// ASan + UBSan.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -76,6 +78,54 @@ FS_CO_HD uint32_t table_slots(uint32_t n) {
     uint32_t t = 2;
     while (t < 2u * n) t <<= 1;  // (n <= 2^30: t <= 2^31)
     return t;
+}
+
+// ---- The keyed table of a connection list (the delivery's sockets, the close call's closers, the
+// connect call's openers): table_slots(n) slots, each a record's index or kEmpty, built on the host and
+// staged with the records. A key starts probing at its hash & hash_mask (all ones in the product) and
+// goes on linearly; the result of a lookup does not depend on the hash. Rec: a record that begins with
+// the 13 key bytes as `uint8_t key[13]` (fs_rx_sock, fs_cl_sock, fs_cn_sock).
+// The 13 bytes as the key record of the connection's frames: same_key() compares the two.
+FS_CO_HD Key wire_key(const uint8_t key[kKeyBytes]) {
+    Key k;
+    k.w[0] = key[0] | ((uint32_t)key[1] << 8) | ((uint32_t)key[2] << 16) | ((uint32_t)key[3] << 24);
+    k.w[1] = key[4] | ((uint32_t)key[5] << 8) | ((uint32_t)key[6] << 16) | ((uint32_t)key[7] << 24);
+    k.w[2] = key[8] | ((uint32_t)key[9] << 8) | ((uint32_t)key[10] << 16) | ((uint32_t)key[11] << 24);
+    k.w[3] = key[12] | kKeyAccepted;
+    return k;
+}
+FS_CO_HD uint32_t table_start(const Key& k, uint32_t hash_mask, uint32_t tmask) { return key_hash(k) & hash_mask & tmask; }
+// The record whose key equals `key`, or kEmpty. At most every slot once.
+template <class Rec>
+FS_CO_HD uint32_t lookup(const Key& key, const Rec* recs, const uint32_t* table, uint32_t tmask, uint32_t hash_mask) {
+    uint32_t s = table_start(key, hash_mask, tmask);
+    for (uint32_t probe = 0; probe <= tmask; ++probe) {
+        const uint32_t owner = table[s];
+        if (owner == kEmpty) return kEmpty;
+        if (same_key(key, wire_key(recs[owner].key))) return owner;
+        s = (s + 1u) & tmask;
+    }
+    return kEmpty;
+}
+// Fills `table` (table_slots(n) entries). Returns kEmpty, or the first record whose key an earlier
+// record has already.
+template <class Rec>
+inline uint32_t build_table(const Rec* recs, uint32_t n, uint32_t hash_mask, uint32_t* table) {
+    const uint32_t slots = table_slots(n), tmask = slots - 1u;
+    for (uint32_t i = 0; i < slots; ++i) table[i] = kEmpty;
+    for (uint32_t i = 0; i < n; ++i) {
+        const Key key = wire_key(recs[i].key);
+        uint32_t s = table_start(key, hash_mask, tmask);
+        for (uint32_t probe = 0; probe <= tmask; ++probe) {
+            if (table[s] == kEmpty) {
+                table[s] = i;
+                break;
+            }
+            if (same_key(key, wire_key(recs[table[s]].key))) return i;
+            s = (s + 1u) & tmask;
+        }
+    }
+    return kEmpty;
 }
 
 // The sort key. b = bit_width(n) bits hold a frame index; an accepted frame's key is the batch

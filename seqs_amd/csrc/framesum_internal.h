@@ -170,20 +170,21 @@ struct RecvScratch {
 struct AcceptScratch {
     uint64_t rank_in, rank_sorted, synrec, cand_frame, sort_temp, sort_bytes, bytes;
 };
-// CloseScratch: 16-byte aligned; 20 bytes per frame and 4 per closer.
-struct CloseScratch {
-    uint64_t sq, flow_closer, closer_first, bytes;
+// OwnerScratch: what the match and the gather of the close and of the connect call fill (framesum_match_dev.h:
+// an "owner" is a closer or an opener), 16-byte aligned; 20 bytes per frame and 4 per owner. The close call's
+// scratch is this; the connect call's has its reply records (`reprec`, 88 per opener, 8-byte aligned) behind it.
+struct OwnerScratch {
+    uint64_t sq, flow_owner, owner_first, bytes;
+};
+struct ConnectScratch : OwnerScratch {
+    uint64_t reprec;
 };
 CoScratch coalesce_scratch(uint32_t n);
 FlowScratch flows_scratch(uint32_t n);
 DeliverScratch deliver_scratch(uint32_t n, uint32_t n_socks);
 RecvScratch recv_scratch(uint32_t n);
 AcceptScratch accept_scratch(uint32_t n, uint32_t n_listeners, uint32_t n_slots);
-// ConnectScratch: 16-byte aligned; 20 bytes per frame and 92 per opener.
-struct ConnectScratch {
-    uint64_t sq, reprec, flow_opener, opener_first, bytes;
-};
-CloseScratch close_scratch(uint32_t n, uint32_t n_closers);
+OwnerScratch owner_scratch(uint32_t n, uint32_t n_owners);
 ConnectScratch connect_scratch(uint32_t n, uint32_t n_openers);
 
 // What the accept call has beside a receive call's batch and results: the counts of its staged lists and
@@ -233,7 +234,7 @@ struct RxLeft {
     uint8_t* accept_scratch;
     AcceptScratch acs;
     uint8_t* close_scratch;
-    CloseScratch cs;
+    OwnerScratch cs;
     uint8_t* connect_scratch;
     ConnectScratch cns;
 };
@@ -273,6 +274,11 @@ hipError_t launch_accept(const RxBatch& b, const RxAccept& x, const RxLeft& left
 // socket. y.ctl_code is zeroed by the caller. With n of 0 only the out records are written.
 hipError_t launch_close(const RxBatch& b, const RxResults& r, const RxClose& y, const RxLeft& left, const uint8_t* d_block,
                         const RxLaunch& how);
+// The gather of the close and of the connect call (framesum_close.hip), one launch behind the call's match: per
+// slot of a flow whose owner is below n_owners, Seq, Ack, the dword at L4 + 12 and the payload length into
+// `scratch` laid out as `s`. Enqueues only: the caller asks for the last error behind its launches.
+void launch_flow_gather_sq(const RxBatch& b, const RxLeft& left, uint8_t* scratch, const OwnerScratch& s, uint32_t n_owners,
+                           const RxLaunch& how);
 
 // The launches that follow a batch's close launches (fs_connect_flows_batch in include/framesum_connect.h)
 // and read what the flow launches left. `d_block`: the device copy of the staged block (framesum_connect.h

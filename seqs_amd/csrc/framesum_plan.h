@@ -219,7 +219,7 @@ inline void host_chunks(const uint64_t* offsets, const uint32_t* lengths, uint32
 // ---------------------------------------------------------------------------------------
 // The device result arrays of the seven RX host forms (fs_coalesce_batch_host,
 // fs_coalesce_flows_batch_host, fs_deliver_flows_batch_host, fs_recv_flows_batch_host and, with the
-// arrays of their own in the second, the third and the fourth table below, fs_accept_flows_batch_host,
+// arrays of their own in the second table below, fs_accept_flows_batch_host,
 // fs_close_flows_batch_host and fs_connect_flows_batch_host), described
 // once: which arrays a call kind has, what each is sized by, where each lies in the context's one
 // buffer, and how much of each comes back given the totals the device reported. The host forms carve
@@ -292,102 +292,61 @@ constexpr uint64_t bytes_back(Kind kind, Array a, uint64_t n, uint64_t n_socks, 
     return kind < kArrayDesc[a].from ? 0 : elem_bytes(kind, a) * count_of(kArrayDesc[a].back, n, n_socks, t);
 }
 
-// The fifth kind's own arrays (fs_accept_flows_batch_host: the kind has every array above, and these),
-// described the same way in a table of their own: what counts an array's entries, where each lies behind
-// the arrays above in the same buffer, and whether the caller's bytes go to the device first (the call
-// writes only the filled slots' entries of those, and every array comes back whole).
-enum AcceptArray : uint32_t { kConns, kListenersOut, kAcceptOf, kSynacks, kSynackOut, kSynackStatus, kAcceptArrays };
-enum AcceptCount : uint32_t { kPerSlot, kPerListener, kPerFrameOfBatch };
-struct AcceptArrayDesc {
-    uint32_t elem, align;  // bytes per entry, and the alignment the kernels' stores want
-    AcceptCount count;
+// The own arrays of the fifth, the sixth and the seventh kind (fs_accept_flows_batch_host,
+// fs_close_flows_batch_host, fs_connect_flows_batch_host: each has every array above, those of the kinds
+// before it, and its own), described the same way in one table: which kind brings an array, what counts
+// its entries, the alignment the kernels' stores want, and whether the caller's bytes go to the device
+// first (the call writes only some entries of those -- the filled slots', the openers' with a reply --
+// and every array comes back whole). They lie behind the arrays above in the same buffer, in this order.
+enum ExtraArray : uint32_t {
+    kConns, kListenersOut, kAcceptOf, kSynacks, kSynackOut, kSynackStatus,  // kAccept
+    kClosersOut, kSocksClose, kCtlCode,                                      // kClose
+    kOpenersOut, kReplies, kReplyOut, kReplyStatus,                          // kConnect
+    kExtraArrays,
+};
+enum ExtraCount : uint32_t { kPerSlot, kPerListener, kPerCloser, kPerSocket, kPerOpener, kPerBatchFrame, kExtraCounts };
+struct ExtraArrayDesc {
+    Kind from;             // the kind that brings the array
+    uint32_t elem, align;  // bytes per entry, and the alignment
+    ExtraCount count;
     bool goes_in;
 };
-constexpr AcceptArrayDesc kAcceptArrayDesc[kAcceptArrays] = {
-    {48, 4, kPerSlot, false},          // fs_accept_conn
-    {16, 4, kPerListener, false},      // fs_listener_out
-    {4, 4, kPerFrameOfBatch, false},   // accept_of
-    {64, 1, kPerSlot, true},           // synacks (FS_ACCEPT_STRIDE)
-    {8, 8, kPerSlot, true},            // synack_out
-    {1, 1, kPerSlot, true},            // synack_status
+constexpr ExtraArrayDesc kExtraArrayDesc[kExtraArrays] = {
+    {kAccept, 48, 4, kPerSlot, false},         // fs_accept_conn
+    {kAccept, 16, 4, kPerListener, false},     // fs_listener_out
+    {kAccept, 4, 4, kPerBatchFrame, false},    // accept_of
+    {kAccept, 64, 1, kPerSlot, true},          // synacks (FS_ACCEPT_STRIDE)
+    {kAccept, 8, 8, kPerSlot, true},           // synack_out
+    {kAccept, 1, 1, kPerSlot, true},           // synack_status
+    {kClose, 32, 4, kPerCloser, false},        // fs_cl_out, per closer
+    {kClose, 32, 4, kPerSocket, false},        // fs_cl_out, per listed socket
+    {kClose, 1, 1, kPerBatchFrame, false},     // ctl_code
+    {kConnect, 48, 4, kPerOpener, false},      // fs_cn_out
+    {kConnect, 64, 1, kPerOpener, true},       // replies (FS_ACCEPT_STRIDE)
+    {kConnect, 8, 8, kPerOpener, true},        // reply_out
+    {kConnect, 1, 1, kPerOpener, true},        // reply_status
 };
-struct AcceptLayout {
-    uint64_t at[kAcceptArrays], room[kAcceptArrays], bytes;  // `bytes`: the arrays above and these
+struct ExtraCounts {
+    uint64_t of[kExtraCounts];  // by ExtraCount
 };
-// `base`: layout(kAccept, n, n_socks).bytes.
-inline AcceptLayout accept_layout(uint64_t base, uint64_t n, uint64_t n_listeners, uint64_t n_slots) {
-    AcceptLayout L;
+struct ExtraLayout {
+    uint64_t at[kExtraArrays], room[kExtraArrays], bytes;  // `bytes`: `base` and the rows laid out
+    bool has(ExtraArray a) const { return at[a] != kAbsent; }
+};
+// The rows whose kind lies in [first, last] (none when last < first), from `base` on:
+// layout(kind, n, n_socks).bytes with first = kAccept and last = the call's kind; 0 with both kConnect for
+// a connect call without a batch, which has these arrays alone.
+inline ExtraLayout extra_layout(Kind first, Kind last, uint64_t base, const ExtraCounts& counts) {
+    ExtraLayout L;
     uint64_t at = base;
-    for (uint32_t a = 0; a < kAcceptArrays; ++a) {
-        const AcceptArrayDesc& d = kAcceptArrayDesc[a];
+    for (uint32_t a = 0; a < kExtraArrays; ++a) {
+        const ExtraArrayDesc& d = kExtraArrayDesc[a];
+        L.at[a] = kAbsent;
+        L.room[a] = 0;
+        if (d.from < first || d.from > last) continue;
         at = (at + d.align - 1) / d.align * d.align;
         L.at[a] = at;
-        L.room[a] = d.elem * (d.count == kPerSlot ? n_slots : d.count == kPerListener ? n_listeners : n);
-        at += L.room[a];
-    }
-    L.bytes = at;
-    return L;
-}
-
-// The sixth kind's own arrays (fs_close_flows_batch_host: the kind has every array above, and these), in
-// a third table: each lies behind the accept call's arrays in the same buffer, none goes to the device
-// first, and every one comes back whole.
-enum CloseArray : uint32_t { kClosersOut, kSocksClose, kCtlCode, kCloseArrays };
-enum CloseCount : uint32_t { kPerCloser, kPerSockOfCall, kPerFrameOfCall };
-struct CloseArrayDesc {
-    uint32_t elem, align;  // bytes per entry, and the alignment the kernels' stores want
-    CloseCount count;
-};
-constexpr CloseArrayDesc kCloseArrayDesc[kCloseArrays] = {
-    {32, 4, kPerCloser},       // fs_cl_out, per closer
-    {32, 4, kPerSockOfCall},   // fs_cl_out, per listed socket
-    {1, 1, kPerFrameOfCall},   // ctl_code
-};
-struct CloseLayout {
-    uint64_t at[kCloseArrays], room[kCloseArrays], bytes;  // `bytes`: the arrays above and these
-};
-// `base`: accept_layout(...).bytes.
-inline CloseLayout close_layout(uint64_t base, uint64_t n, uint64_t n_socks, uint64_t n_closers) {
-    CloseLayout L;
-    uint64_t at = base;
-    for (uint32_t a = 0; a < kCloseArrays; ++a) {
-        const CloseArrayDesc& d = kCloseArrayDesc[a];
-        at = (at + d.align - 1) / d.align * d.align;
-        L.at[a] = at;
-        L.room[a] = d.elem * (d.count == kPerCloser ? n_closers : d.count == kPerSockOfCall ? n_socks : n);
-        at += L.room[a];
-    }
-    L.bytes = at;
-    return L;
-}
-
-// The seventh kind's own arrays (fs_connect_flows_batch_host: the kind has every array above, and these),
-// in a fourth table: each lies behind the close call's arrays in the same buffer; the reply arrays go to
-// the device first (the call writes only the entries of openers with a reply), and every one comes back
-// whole.
-enum ConnectArray : uint32_t { kOpenersOut, kReplies, kReplyOut, kReplyStatus, kConnectArrays };
-struct ConnectArrayDesc {
-    uint32_t elem, align;  // bytes per opener, and the alignment the kernels' stores want
-    bool goes_in;
-};
-constexpr ConnectArrayDesc kConnectArrayDesc[kConnectArrays] = {
-    {48, 4, false},  // fs_cn_out
-    {64, 1, true},   // replies (FS_ACCEPT_STRIDE)
-    {8, 8, true},    // reply_out
-    {1, 1, true},    // reply_status
-};
-struct ConnectLayout {
-    uint64_t at[kConnectArrays], room[kConnectArrays], bytes;  // `bytes`: the arrays above and these
-};
-// `base`: close_layout(...).bytes (0 for a call without a batch: these arrays alone).
-inline ConnectLayout connect_layout(uint64_t base, uint64_t n_openers) {
-    ConnectLayout L;
-    uint64_t at = base;
-    for (uint32_t a = 0; a < kConnectArrays; ++a) {
-        const ConnectArrayDesc& d = kConnectArrayDesc[a];
-        at = (at + d.align - 1) / d.align * d.align;
-        L.at[a] = at;
-        L.room[a] = d.elem * n_openers;
+        L.room[a] = d.elem * counts.of[d.count];
         at += L.room[a];
     }
     L.bytes = at;

@@ -218,12 +218,12 @@ hipError_t launch_recv(const RxBatch& b, const RxResults& r, const RxLeft& left,
     a.snd_out = r.snd_out();
     a.code = r.code();
     a.n = n;
-    a.n_blocks = (uint32_t)(((uint64_t)n + kScanBlock - 1) / kScanBlock);
+    const ScanGrid g = scan_grid(n, how);
+    a.n_blocks = g.blocks;
     a.n_socks = n_socks;
-    const uint32_t cap = (uint32_t)(how.max_workgroups > 0 ? how.max_workgroups : 1);
     const uint32_t walk_blocks = (n_socks + kWaves - 1u) / kWaves;
-    if (n != 0) hipLaunchKernelGGL(recv_gather, dim3(a.n_blocks < cap ? a.n_blocks : cap), dim3(kThreads), 0, stream, a);
-    hipLaunchKernelGGL(recv_walk, dim3(walk_blocks < cap ? walk_blocks : cap), dim3(kThreads), 0, stream, a);
+    if (n != 0) hipLaunchKernelGGL(recv_gather, dim3(g.scan), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(recv_walk, dim3(g.capped(walk_blocks)), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -222,6 +222,41 @@ def mixed():
                  socks=est.socks, snd=est.snd, rings_bytes=est.rings_bytes, traces=[t for _, _, t in flows])
 
 
+def three_lists():
+    """All three keyed lists in one batch: 2 listed sockets, 2 closers and 2 openers, whose six TCP flows are
+    interleaved with one TCP flow and one UDP flow that match nothing, and a listener with two slots that no
+    frame reaches (its SYN-ACK arrays must come back as they went in). The first socket's, the first closer's
+    and the first opener's flow have 66 slots each, so each of their walks crosses a chunk boundary (three
+    flows of more than 64 slots: 211 frames in all); the events lie behind it, in slots 64 and 65."""
+    rng = np.random.default_rng(9780)
+    snd_nxt, una = 7000, 6990
+    sh = [acases.header(rng, 0x2D00 + j, port=8080) for j in range(2)]
+    nxt = [M32 - 150, 500]
+    # socket 0: data and pure ACKs up to a FIN in slot 64, a pure ACK in CloseWait behind it; socket 1: an RST that passes
+    long_flow, seq = [], nxt[0]
+    for k in range(64):
+        pay = rcases.data(rng, 1 + k % 7) if k % 3 == 0 else b""
+        long_flow.append(rcases.frame(sh[0], seq, una + 1 + k % 5, ACK | (PSH if pay else 0), 300 + k, pay))
+        seq = (seq + len(pay)) % M32
+    long_flow.append(rcases.frame(sh[0], seq, una + 3, FIN | ACK, 999))
+    long_flow.append(ccases.make(sh[0], "ack", close_ref.Ctl(9, (seq + 1) % M32, 0, 0), snd_nxt, 1))
+    short_flow = [rcases.frame(sh[1], nxt[1], una + 1, ACK, 300), rcases.frame(sh[1], nxt[1], 0, RST, 0),
+                  rcases.frame(sh[1], nxt[1], una + 2, ACK, 301)]
+    socks = dref.socks_of(*[dref.sock(dref.key_of_header(h), x, 256 * j, 256, snd_nxt=snd_nxt) for j, (h, x) in enumerate(zip(sh, nxt))])
+    cf = [ccases.script(acases.header(rng, 0x2D10), 5, M32 - 3, 41, 50, 66, {3: "ack", 65: "fin_ack_nxt"}),
+          ccases.script(acases.header(rng, 0x2D11), 9, 900, 41, 50, 3, {1: "fin"})]
+    of = [script(acases.header(rng, 0x2D20, port=46100), 77, 66, {64: "synack"}),
+          script(acases.header(rng, 0x2D21, port=46101), M32 - 1, 3, {1: "syn"}, flags=1)]
+    stray = fref.flow_header(rng, 0x2D30)
+    stray_tcp = [fref.tcp_frame(stray, 10, b"nobody's"), fref.tcp_frame(stray, 18, b"either")]
+    udp = fref.udp_frame(rng, b"datagram 1")
+    stray_udp = [udp, udp[:42] + b"datagram 2"]
+    frames = fref.finish(interleaved([long_flow, cf[0][0], of[0][0], short_flow, cf[1][0], of[1][0], stray_tcp, stray_udp]))
+    return NCase(frames, ref.openers_of(*[r for _, r, _ in of]), closers=close_ref.closers_of(*[r for _, r, _ in cf]), socks=socks,
+                 snd=recv_ref.snd_of(*[(una, 444)] * 2), rings_bytes=512, traces=[t for _, _, t in of],
+                 listeners=accept_ref.listeners_of((acases.local(81), acases.MAC, 0, 2)), slots=acases.default_slots(2))
+
+
 def near_keys():
     """Opener 0 and 12 flows whose keys differ from its key in one bit (one per key byte behind the protocol),
     each a SYN-ACK that would open it: none is the opener's."""

@@ -12,6 +12,7 @@
 #include "../../seqs_amd/csrc/framesum_close.h"
 
 namespace cl = framesum::closing;
+namespace fl = framesum::flows;
 namespace dl = framesum::deliver;
 
 static int g_failed = 0;
@@ -154,14 +155,14 @@ static void test_closer_table() {
             for (uint32_t i = 0; i < n; ++i) list[i] = closer(i, (uint8_t)(5 + i % 6));
             const uint32_t slots = cl::table_slots(n);
             uint32_t* table = static_cast<uint32_t*>(std::malloc(4ull * slots));
-            CHECK(cl::build_closer_table(list, n, mask, table) == cl::kNone);
+            CHECK(fl::build_table(list, n, mask, table) == cl::kNone);
             uint32_t filled = 0;
             for (uint32_t s = 0; s < slots; ++s) filled += table[s] != cl::kNone;
             CHECK(filled == n);
-            for (uint32_t i = 0; i < n; ++i) CHECK(cl::lookup_closer(cl::closer_key(list[i]), list, table, slots - 1u, mask) == i);
+            for (uint32_t i = 0; i < n; ++i) CHECK(fl::lookup(fl::wire_key(list[i].key), list, table, slots - 1u, mask) == i);
             for (uint32_t i = n; i < n + 50u; ++i) {
                 const fs_cl_sock other = closer(i);
-                CHECK(cl::lookup_closer(cl::closer_key(other), list, table, slots - 1u, mask) == cl::kNone);
+                CHECK(fl::lookup(fl::wire_key(other.key), list, table, slots - 1u, mask) == cl::kNone);
             }
             // the staged block holds the records, the table and the sockets' fixed values
             fs_rx_sock socks[3];
@@ -178,7 +179,7 @@ static void test_closer_table() {
             // a duplicate is found wherever it stands
             if (n > 1) {
                 list[n - 1] = list[n / 2 - (n / 2 == n - 1 ? 1 : 0)];
-                CHECK(cl::build_closer_table(list, n, mask, table) == n - 1);
+                CHECK(fl::build_table(list, n, mask, table) == n - 1);
             }
             std::free(block), std::free(table), std::free(list);
         }

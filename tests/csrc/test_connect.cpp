@@ -13,6 +13,7 @@
 #include "../../seqs_amd/csrc/framesum_connect.h"
 
 namespace cn = framesum::connect;
+namespace fl = framesum::flows;
 namespace cl = framesum::closing;
 namespace dl = framesum::deliver;
 namespace ac = framesum::accept;
@@ -140,18 +141,18 @@ static void test_opener_table() {
             for (uint32_t i = 0; i < n; ++i) list[i] = opener(i);
             const uint32_t slots = cn::table_slots(n);
             uint32_t* table = static_cast<uint32_t*>(std::malloc(4ull * slots));
-            CHECK(cn::build_opener_table(list, n, mask, table) == cn::kNone);
+            CHECK(fl::build_table(list, n, mask, table) == cn::kNone);
             uint32_t filled = 0;
             for (uint32_t s = 0; s < slots; ++s) filled += table[s] != cn::kNone;
             CHECK(filled == n);
-            for (uint32_t i = 0; i < n; ++i) CHECK(cn::lookup_opener(cn::opener_key(list[i]), list, table, slots - 1u, mask) == i);
+            for (uint32_t i = 0; i < n; ++i) CHECK(fl::lookup(fl::wire_key(list[i].key), list, table, slots - 1u, mask) == i);
             for (uint32_t i = n; i < n + 50u; ++i)
-                CHECK(cn::lookup_opener(cn::opener_key(opener(i)), list, table, slots - 1u, mask) == cn::kNone);
+                CHECK(fl::lookup(fl::wire_key(opener(i).key), list, table, slots - 1u, mask) == cn::kNone);
             // one bit away from a listed key, in every key byte behind the protocol
             for (uint32_t b = 1; b < 13; ++b) {
                 fs_cn_sock near = list[n / 2];
                 near.key[b] ^= (uint8_t)(1u << (b % 8));
-                const uint32_t hit = cn::lookup_opener(cn::opener_key(near), list, table, slots - 1u, mask);
+                const uint32_t hit = fl::lookup(fl::wire_key(near.key), list, table, slots - 1u, mask);
                 CHECK(hit == cn::kNone || std::memcmp(list[hit].key, near.key, 13) == 0);
             }
             // the staged block holds the records, then the table
@@ -162,7 +163,7 @@ static void test_opener_table() {
             CHECK(std::memcmp(block, list, b.table) == 0 && std::memcmp(block + b.table, table, 4ull * slots) == 0);
             if (n > 1) {  // a duplicate is found wherever it stands
                 list[n - 1] = list[n / 2 - (n / 2 == n - 1 ? 1 : 0)];
-                CHECK(cn::build_opener_table(list, n, mask, table) == n - 1);
+                CHECK(fl::build_table(list, n, mask, table) == n - 1);
             }
             std::free(block), std::free(table), std::free(list);
         }

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../seqs_amd/csrc/framesum_connect.h"
 #include "../../seqs_amd/csrc/framesum_deliver.h"
 
 namespace dl = framesum::deliver;
@@ -99,32 +100,82 @@ static void test_table() {
             uint32_t* table = (uint32_t*)std::malloc(4ull * slots);  // exactly sized
             fs_rx_sock* recs = (fs_rx_sock*)std::malloc(sizeof(fs_rx_sock) * n);
             std::memcpy(recs, socks.data(), sizeof(fs_rx_sock) * n);
-            CHECK(dl::build_table(recs, n, mask, table) == dl::kNone);
+            CHECK(fl::build_table(recs, n, mask, table) == dl::kNone);
             uint32_t used = 0;
             for (uint32_t s = 0; s < slots; ++s) used += table[s] != dl::kNone;
             CHECK(used == n);
-            for (uint32_t i = 0; i < n; ++i) CHECK(dl::lookup(dl::sock_key(recs[i]), recs, table, slots - 1, mask) == i);
+            for (uint32_t i = 0; i < n; ++i) CHECK(fl::lookup(fl::wire_key(recs[i].key), recs, table, slots - 1, mask) == i);
             // keys that differ from a socket's in one byte, and a key the frames' records never carry
             for (uint32_t at = 0; at < 13; ++at) {
                 fs_rx_sock other = recs[n / 2];
                 other.key[at] ^= 0x40;
                 bool is_another = false;
                 for (uint32_t i = 0; i < n; ++i) is_another |= std::memcmp(other.key, recs[i].key, 13) == 0;
-                if (!is_another) CHECK(dl::lookup(dl::sock_key(other), recs, table, slots - 1, mask) == dl::kNone);
+                if (!is_another) CHECK(fl::lookup(fl::wire_key(other.key), recs, table, slots - 1, mask) == dl::kNone);
             }
             // a frame's key record equals the socket's whatever its byte 15 and bytes 13, 14 say
-            fl::Key k = dl::sock_key(recs[0]);
+            fl::Key k = fl::wire_key(recs[0].key);
             k.w[3] &= 0xFFu;
-            CHECK(dl::lookup(k, recs, table, slots - 1, mask) == 0);
+            CHECK(fl::lookup(k, recs, table, slots - 1, mask) == 0);
             // an equal key is found by the build
             if (n > 1) {
                 std::memcpy(recs[n - 1].key, recs[0].key, 13);
-                CHECK(dl::build_table(recs, n, mask, table) == n - 1);
+                CHECK(fl::build_table(recs, n, mask, table) == n - 1);
             }
             std::free(table);
             std::free(recs);
         }
     CHECK(dl::block_of(3).table == 144 && dl::block_of(3).bytes == 144 + 4 * 8);
+}
+
+// The one table template (framesum_flows.h) over the three record types that begin with the 13 key bytes:
+// the same keys give the same table, the same lookups and the same duplicate, whatever else a record holds
+// and however long it is. Exactly sized heap arrays again.
+template <class Rec>
+static Rec* keyed_list(const std::vector<fs_rx_sock>& keys, uint8_t fill) {
+    Rec* recs = (Rec*)std::malloc(sizeof(Rec) * keys.size());
+    std::memset(recs, fill, sizeof(Rec) * keys.size());  // (the rest of a record does not matter)
+    for (size_t i = 0; i < keys.size(); ++i) std::memcpy(recs[i].key, keys[i].key, 13);
+    return recs;
+}
+static void test_one_table_for_all_records() {
+    for (uint32_t mask : {0u, 1u, 0xFFu, 0xFFFFFFFFu})
+        for (uint32_t n : {1u, 2u, 3u, 64u, 65u}) {
+            std::vector<fs_rx_sock> keys;
+            for (uint32_t i = 0; i < n; ++i) keys.push_back(sock(104729u * i + 5u, 0, 1));
+            const fs_rx_sock absent = sock(104729u * n + 5u, 0, 1);
+            fs_rx_sock* rx = keyed_list<fs_rx_sock>(keys, 0x00);
+            fs_cl_sock* cl = keyed_list<fs_cl_sock>(keys, 0x5A);
+            fs_cn_sock* cn = keyed_list<fs_cn_sock>(keys, 0xFF);
+            const uint32_t slots = fl::table_slots(n);
+            uint32_t* t_rx = (uint32_t*)std::malloc(4ull * slots);
+            uint32_t* t_cl = (uint32_t*)std::malloc(4ull * slots);
+            uint32_t* t_cn = (uint32_t*)std::malloc(4ull * slots);
+            CHECK(fl::build_table(rx, n, mask, t_rx) == dl::kNone);
+            CHECK(fl::build_table(cl, n, mask, t_cl) == dl::kNone);
+            CHECK(fl::build_table(cn, n, mask, t_cn) == dl::kNone);
+            CHECK(std::memcmp(t_rx, t_cl, 4ull * slots) == 0 && std::memcmp(t_rx, t_cn, 4ull * slots) == 0);
+            for (uint32_t i = 0; i < n; ++i) {
+                const fl::Key k = fl::wire_key(keys[i].key);
+                CHECK(fl::lookup(k, rx, t_rx, slots - 1, mask) == i);
+                CHECK(fl::lookup(k, cl, t_cl, slots - 1, mask) == i);
+                CHECK(fl::lookup(k, cn, t_cn, slots - 1, mask) == i);
+            }
+            const fl::Key none = fl::wire_key(absent.key);
+            CHECK(fl::lookup(none, rx, t_rx, slots - 1, mask) == dl::kNone);
+            CHECK(fl::lookup(none, cl, t_cl, slots - 1, mask) == dl::kNone);
+            CHECK(fl::lookup(none, cn, t_cn, slots - 1, mask) == dl::kNone);
+            if (n > 1) {  // the last key repeats the first
+                std::memcpy(rx[n - 1].key, rx[0].key, 13);
+                std::memcpy(cl[n - 1].key, cl[0].key, 13);
+                std::memcpy(cn[n - 1].key, cn[0].key, 13);
+                CHECK(fl::build_table(rx, n, mask, t_rx) == n - 1);
+                CHECK(fl::build_table(cl, n, mask, t_cl) == n - 1);
+                CHECK(fl::build_table(cn, n, mask, t_cn) == n - 1);
+            }
+            std::free(t_rx), std::free(t_cl), std::free(t_cn);
+            std::free(rx), std::free(cl), std::free(cn);
+        }
 }
 
 static bool admit(dl::State st, uint32_t seq, uint32_t ack, uint32_t len, uint32_t flags, uint32_t wnd, uint32_t snd) {
@@ -204,6 +255,7 @@ static void test_wrap_split() {
 int main() {
     test_checks();
     test_table();
+    test_one_table_for_all_records();
     test_admission();
     test_wrap_split();
     if (g_failed) {

@@ -479,8 +479,70 @@ static void check_rx_arrays(uint32_t kind_index, uint64_t n, uint64_t n_socks) {
     }
 }
 
+// The own arrays of the accept, the close and the connect call (plan::rx::extra_layout): the thirteen rows
+// stated here again in the buffer's order -- the accept call's six, the close call's three, the connect
+// call's four -- each laid out behind the one before it at its alignment, from the end of the kind's
+// arrays above; a kind has the rows of the kinds up to it and no other; and the offsets of one case as numbers.
+static void check_extra_arrays(uint32_t kind_index, uint64_t n, uint64_t n_socks, uint64_t n_listeners, uint64_t n_slots,
+                               uint64_t n_closers, uint64_t n_openers) {
+    namespace rx = framesum::plan::rx;
+    struct Want {
+        uint32_t from;  // 4 accept, 5 close, 6 connect
+        uint64_t elem, align, count;
+        bool goes_in;
+    };
+    const Want want[] = {{4, 48, 4, n_slots, false},  {4, 16, 4, n_listeners, false}, {4, 4, 4, n, false},
+                         {4, 64, 1, n_slots, true},   {4, 8, 8, n_slots, true},       {4, 1, 1, n_slots, true},
+                         {5, 32, 4, n_closers, false}, {5, 32, 4, n_socks, false},     {5, 1, 1, n, false},
+                         {6, 48, 4, n_openers, false}, {6, 64, 1, n_openers, true},    {6, 8, 8, n_openers, true},
+                         {6, 1, 1, n_openers, true}};
+    CHECK(sizeof want / sizeof want[0] == rx::kExtraArrays);
+    const rx::ExtraCounts counts{{n_slots, n_listeners, n_closers, n_socks, n_openers, n}};
+    const uint64_t base = rx::layout((rx::Kind)kind_index, n, n_socks).bytes;
+    const rx::ExtraLayout L = rx::extra_layout(rx::kAccept, (rx::Kind)kind_index, base, counts);
+    const rx::ExtraLayout alone = rx::extra_layout(rx::kConnect, rx::kConnect, 0, counts);  // the call without a batch
+    uint64_t at = base, at_alone = 0;
+    for (uint32_t a = 0; a < rx::kExtraArrays; ++a) {
+        const Want& w = want[a];
+        CHECK(rx::kExtraArrayDesc[a].goes_in == w.goes_in);
+        if (w.from == 6) {
+            at_alone = (at_alone + w.align - 1) / w.align * w.align;
+            CHECK(alone.at[a] == at_alone && alone.room[a] == w.elem * w.count);
+            at_alone += w.elem * w.count;
+        } else {
+            CHECK(!alone.has((rx::ExtraArray)a) && alone.room[a] == 0);
+        }
+        if (kind_index < w.from) {
+            CHECK(!L.has((rx::ExtraArray)a) && L.room[a] == 0);
+            continue;
+        }
+        at = (at + w.align - 1) / w.align * w.align;
+        CHECK(L.at[a] == at && L.room[a] == w.elem * w.count);
+        at += w.elem * w.count;
+    }
+    CHECK(L.bytes == at && alone.bytes == at_alone);
+}
+static void check_extra_arrays_by_number() {
+    namespace rx = framesum::plan::rx;
+    // 141 frames, 7 sockets, 3 listeners, 5 slots, 2 closers, 9 openers
+    const rx::ExtraCounts counts{{5, 3, 2, 7, 9, 141}};
+    CHECK(rx::layout(rx::kConnect, 141, 7).bytes == 9781);
+    const rx::ExtraLayout L = rx::extra_layout(rx::kAccept, rx::kConnect, 9781, counts);
+    const uint64_t at[] = {9784, 10024, 10072, 10636, 10960, 11000, 11008, 11072, 11296, 11440, 11872, 12448, 12520};
+    for (uint32_t a = 0; a < rx::kExtraArrays; ++a) CHECK(L.at[a] == at[a]);
+    CHECK(L.bytes == 12529);
+    const rx::ExtraLayout alone = rx::extra_layout(rx::kConnect, rx::kConnect, 0, counts);
+    CHECK(alone.at[rx::kOpenersOut] == 0 && alone.at[rx::kReplies] == 432 && alone.at[rx::kReplyOut] == 1008 &&
+          alone.at[rx::kReplyStatus] == 1080 && alone.bytes == 1089);
+}
+
 int main() {
     std::mt19937_64 rng(12345);
+    for (uint32_t kind = 0; kind < 7; ++kind)
+        for (uint64_t n : {uint64_t(1), uint64_t(3), uint64_t(141), uint64_t(65793)})
+            for (uint64_t lists : {uint64_t(0), uint64_t(1), uint64_t(3), uint64_t(65536)})
+                check_extra_arrays(kind, n, lists, lists ? lists - 1 : 2, lists + 1, lists ? 5 : 0, lists * 3);
+    check_extra_arrays_by_number();
     for (uint32_t kind = 0; kind < 4; ++kind)
         for (uint64_t n : {uint64_t(0), uint64_t(1), uint64_t(2), uint64_t(3), uint64_t(63), uint64_t(64), uint64_t(65),
                            uint64_t(255), uint64_t(256), uint64_t(257), uint64_t(65793), uint64_t(1) << 30})

@@ -2,7 +2,8 @@
 every rule at every position on both sides of the chunk boundaries with frames behind the walk's end left
 alone, two events in one chunk and across a boundary, the extremes of ISS, Seq, Window and rcv_wnd, the SYN
 of a flagged opener, the header geometries with the MSS kinds, the opener whose flow opens with a SYN to a
-listener, openers beside sockets, closers and listeners, the near keys, and the two big shapes."""
+listener, openers beside sockets, closers and listeners, the three keyed lists with a long flow each, the near
+keys, and the two big shapes."""
 import numpy as np
 import pytest
 
@@ -155,6 +156,24 @@ def test_mixed():
     # the close call's codes are where they were, and this call's lie in the openers' flows only
     mine = e["ctl_code"] != e["close_ctl_code"]
     assert mine.any() and not e["close_ctl_code"][mine].any() and e["close_ctl_code"].any()
+
+
+def test_three_lists():
+    case = cases.three_lists()
+    e, frames = expected(case)
+    check_traces(case, e, frames)
+    assert (len(case.socks), len(case.closers), len(case.openers)) == (2, 2, 2)
+    assert e["n_flows"] == 8 and e["n_accepted"] == len(frames) == 211
+    sizes = {fref.flow_key(frames[int(e["order"][int(fl["first_frame"])])]): int(fl["n_frames"]) for fl in e["flows"]}
+    for lst in (case.socks, case.closers, case.openers):  # the first of each list walks past a chunk boundary
+        assert sizes[bytes(lst["key"][0])] == 66 and sizes[bytes(lst["key"][1])] == 3
+    listed = {bytes(k) for lst in (case.socks, case.closers, case.openers) for k in lst["key"]}
+    assert sorted((k[0], c) for k, c in sizes.items() if k not in listed) == [(6, 2), (17, 2)]
+    # every walk gets behind slot 64 of its flow: the FIN of socket 0 and its CloseWait ACK, closer 0's FIN | ACK, opener 0's SYN-ACK
+    assert int(e["socks_out"]["n_delivered"][0]) == 23 and [int(x) for x in e["socks_close"]["state"]] == [9, 0]
+    assert int(e["socks_close"]["n_taken"][0]) == 1
+    assert [int(x) for x in e["closers_out"]["state"]] == [8, 9] and [int(x) for x in e["openers_out"]["state"]] == [4, 2]
+    assert not e["conns"]["used"].any()
 
 
 def test_near_keys():

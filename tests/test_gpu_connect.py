@@ -225,6 +225,59 @@ def test_hash_masks_and_one_workgroup(eng):
         te.close()
 
 
+def test_three_lists_in_one_call(eng):
+    """Listed sockets, closers and openers in one call (cases.three_lists: the three instantiations of the one
+    match kernel, and the one gather behind the closers' and behind the openers' match), the first of each
+    list with a flow of 66 slots: the device form under the hash masks 0, 1 and all ones with the workgroup cap
+    at 1 and at its default, and the host form, whose arrays keep the caller's bytes outside the written entries."""
+    from seqs_amd import Engine
+    from seqs_amd.framesum import TEST_LIB_PATH
+
+    case = cases.three_lists()
+    e = check(eng, case, seed=21)
+    te = Engine(0, lib_path=TEST_LIB_PATH)
+    try:
+        for workgroups in (1, 0):
+            te.set_workgroups(workgroups)
+            for mask in (0, 1, 0xFFFFFFFF):
+                assert te.lib.fs_test_set_flow_hash_mask(te._ctx, mask) == 0
+                check(te, case, seed=21, e=e, parity=False)
+                host_form_of_three_lists(te, case, e)
+    finally:
+        te.close()
+
+
+def host_form_of_three_lists(eng, case, e, seed=21):
+    """fs_connect_flows_batch_host on check()'s batch and prefills: every array against the restatement `e`."""
+    buf, off, ln = fref.pack(case.frames, lead=1)
+    room = int(ln.sum())
+    noise = np.random.default_rng(77 + seed).integers(0, 256, 3 + room + TAIL, dtype=np.uint8)
+    rings, rep0 = sentinel(case.rings_bytes, seed), reply_prefill(len(case.openers), seed)
+    syn0, out0, st0 = prefill(len(case.slots), seed)
+    from seqs_amd.framesum import DIGEST_DTYPE
+
+    syn_out, syn_st = out0.copy().view(DIGEST_DTYPE).reshape(-1), st0.copy()
+    r = eng.connect_flows_host(buf, off, ln, case.socks, case.snd, rings, case.listeners, case.slots, case.closers, case.openers,
+                               replies=rep0, payload=noise[3 : 3 + room], synacks=syn0, synack_results=(syn_out, syn_st))
+    oout, replies, rout, rst, cout, sclose, ctl, conns, lout, of, synacks, _, _, snd_out, codes, socks_out, marks = r[:17]
+    payload, runs, flows, order, run_of, totals, out, status = r[17:]
+    assert oout.tobytes() == e["openers_out"].tobytes() and np.array_equal(replies, e["replies"])  # (the sentinel tail too)
+    assert rout.tobytes() == e["reply_out"].tobytes() and np.array_equal(rst, e["reply_status"])
+    assert cout.tobytes() == e["closers_out"].tobytes() and sclose.tobytes() == e["socks_close"].tobytes()
+    assert np.array_equal(ctl, e["ctl_code"])
+    assert conns.tobytes() == e["conns"].tobytes() and lout.tobytes() == e["listeners_out"].tobytes()
+    assert np.array_equal(of, e["accept_of"]) and np.array_equal(synacks, e["synacks"])
+    assert syn_out.tobytes() == out0.tobytes() and np.array_equal(syn_st, st0)  # no slot is filled: the caller's bytes
+    assert snd_out.tobytes() == e["snd_out"].tobytes() and np.array_equal(codes, e["code"])
+    assert socks_out.tobytes() == e["socks_out"].tobytes() and np.array_equal(marks, e["delivered"])
+    assert np.array_equal(rings, e["rings"]) and np.array_equal(noise, e["payload"])
+    assert (int(totals["payload_bytes"]), int(totals["n_runs"]), int(totals["n_flows"]), int(totals["n_accepted"])) == \
+        (e["payload_bytes"], e["n_runs"], e["n_flows"], e["n_accepted"])
+    assert runs.tobytes() == e["runs"].tobytes() and flows.tobytes() == e["flows"].tobytes()
+    assert np.array_equal(order, e["order"]) and np.array_equal(run_of, e["run_of"])
+    assert out.tobytes() == e["dig"].tobytes() and np.array_equal(status, e["st"])
+
+
 @pytest.mark.parametrize("variant", engines.VARIANTS, ids=engines.IDS)
 def test_every_engine(variant):
     import torch

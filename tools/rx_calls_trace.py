@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""The HIP calls and the kernels of each of the eight RX entry points (the plain and the flow-aware
-coalesce, the delivery, the receive call; device and host forms), to compare two libraries call for
-call. Measurement tool.
+"""The HIP calls and the kernels of each of the fourteen RX entry points (the plain and the flow-aware
+coalesce, the delivery, the receive, the accept, the close and the connect call; device and host forms),
+to compare two libraries call for call. Measurement tool.
 
   run:  python3 tools/rx_calls_trace.py run
-        two calls of each entry point on the 19-frame batch of tests/test_gpu_host_calls.py
-        (rx_pin_case: three interleaved flows, three sockets), every array passed and allocated before
-        the first call; a torch.cuda.synchronize() (hipDeviceSynchronize, which the library never
+        two calls of each entry point: the first four kinds on the 19-frame batch of
+        tests/test_gpu_host_calls.py (rx_pin_case: three interleaved flows, three sockets), the accept, the
+        close and the connect call on tests/connect_cases.py's mixed() (sockets, listeners, closers and
+        openers in one batch), every array passed and allocated before the first call; a torch.cuda.synchronize() (hipDeviceSynchronize, which the library never
         calls) before the first call and behind each call marks the calls in the trace. The host forms
         run on the context's own stream, where which staging block the receive call's second staged
         launch gets (and so one hipEventQuery more or less) depends on whether the GPU has finished the
@@ -28,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-BASES = ("fs_coalesce_batch", "fs_coalesce_flows_batch", "fs_deliver_flows_batch", "fs_recv_flows_batch")
+BASES = ("fs_coalesce_batch", "fs_coalesce_flows_batch", "fs_deliver_flows_batch", "fs_recv_flows_batch",
+         "fs_accept_flows_batch", "fs_close_flows_batch", "fs_connect_flows_batch")
 NAMES = [b + suffix for b in BASES for suffix in ("", "_host")]
 CALLS_EACH = 2
 BUSY_CYCLES = 20_000_000  # about 10 ms of a spinning kernel in front of each device form
@@ -38,30 +40,48 @@ def run():
     import numpy as np
     import torch
 
+    import connect_cases
+    import flows_ref as fref
     from seqs_amd import Engine
     from test_gpu_host_calls import rx_pin_case
 
     assert torch.cuda.is_available(), "needs a GPU"
     torch.cuda.init()
-    case = rx_pin_case()
-    n, n_socks = case["n"], int(case["socks"].size)
+    pin, mixed = rx_pin_case(), connect_cases.mixed()
+    buf, off, ln = fref.pack(mixed.frames, lead=3)
+    later = dict(buf=buf, off=off, ln=ln, n=int(ln.size), socks=mixed.socks, snd=mixed.snd, room=int(ln.sum()),
+                 noise=np.zeros(int(ln.sum()), dtype=np.uint8), rings=np.zeros(mixed.rings_bytes, dtype=np.uint8))
+    lists = [mixed.listeners, mixed.slots, mixed.closers, mixed.openers]
+    n_listeners, n_slots, n_closers, n_openers = (int(x.size) for x in lists)
     eng = Engine(0)
     stream = torch.cuda.current_stream().cuda_stream
     prepared = []
     for kind, base in enumerate(BASES):
+        case = pin if kind <= 3 else later
+        n, n_socks = case["n"], int(case["socks"].size)
         for host in (False, True):
             sizes = dict(frames=case["buf"], offsets=case["off"].view(np.uint8), lengths=case["ln"].view(np.uint8),
                          payload=case["noise"].copy(), rings=case["rings"].copy())
             sizes.update({k: np.zeros(v, dtype=np.uint8) for k, v in dict(
                 runs=24 * n, flows=32 * n, order=4 * n, run_of=4 * n, totals=24, out=8 * n, status=n, delivered=n, code=n,
-                socks_out=32 * n_socks, snd_out=32 * n_socks).items()})
+                socks_out=32 * n_socks, snd_out=32 * n_socks, conns=48 * n_slots, listeners_out=16 * n_listeners, accept_of=4 * n,
+                synacks=64 * n_slots, synack_out=8 * n_slots, synack_status=n_slots, closers_out=32 * n_closers,
+                socks_close=32 * n_socks, ctl_code=n, openers_out=48 * n_openers, replies=64 * n_openers, reply_out=8 * n_openers,
+                reply_status=n_openers).items()})
             held = sizes if host else {k: torch.from_numpy(v).to("cuda:0") for k, v in sizes.items()}
             at = (lambda k, h=held: h[k].ctypes.data) if host else (lambda k, h=held: h[k].data_ptr())
             args = [eng._ctx, at("frames")] + ([case["buf"].size] if host else []) + [at("offsets"), at("lengths"), n, 0, 0]
             if kind >= 2:
                 args += [case["socks"].ctypes.data, n_socks, at("rings"), case["rings"].size, at("socks_out"), at("delivered")]
-            if kind == 3:
+            if kind >= 3:
                 args += [case["snd"].ctypes.data, at("snd_out"), at("code")]
+            if kind >= 4:
+                args += [lists[0].ctypes.data, n_listeners, lists[1].ctypes.data, n_slots, 0, at("conns"), at("listeners_out"),
+                         at("accept_of"), at("synacks"), at("synack_out"), at("synack_status")]
+            if kind >= 5:
+                args += [lists[2].ctypes.data, n_closers, at("closers_out"), at("socks_close"), at("ctl_code")]
+            if kind >= 6:
+                args += [lists[3].ctypes.data, n_openers, 0, at("openers_out"), at("replies"), at("reply_out"), at("reply_status")]
             args += [at("payload"), case["room"], at("runs")] + ([at("flows"), at("order")] if kind >= 1 else [])
             args += [at("run_of"), at("totals"), at("out"), at("status")] + ([] if host else [stream])
             prepared.append((getattr(eng.lib, base + ("_host" if host else "")), args, held))
