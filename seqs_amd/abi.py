@@ -114,6 +114,17 @@ CN_SEND_SYN = 1  # fs_cn_sock.flags
 CN_REPLY_NONE, CN_REPLY_ACK, CN_REPLY_SYNACK, CN_REPLY_RST, CN_REPLY_SYN = range(5)  # fs_cn_out.reply
 CN_STOP_RST, CN_STOP_SYN = 1, 2  # fs_cn_out.flags
 CONNECT_MAX_OPENERS = 65536
+# The UDP call (include/framesum_udp.h): fs_udp_port (32 bytes), fs_udp_cell (the 32-byte header of a cell) and
+# fs_udp_port_out (32), none with padding
+UDP_PORT_DTYPE = np.dtype([("local", "u1", (6,)), ("reserved", "u1", (2,)), ("n_cells", "<u4"), ("cell_size", "<u4"),
+                           ("cells_off", "<u8"), ("wcell", "<u4"), ("free", "<u4")])
+UDP_CELL_DTYPE = np.dtype([("frame", "<u4"), ("len", "<u2"), ("stored", "<u2"), ("udp_length", "<u2"), ("src_port", "<u2"),
+                           ("src_ip", "u1", (4,)), ("dst_ip", "u1", (4,)), ("src_mac", "u1", (6,)), ("dst_mac", "u1", (6,))])
+UDP_PORT_OUT_DTYPE = np.dtype([("wcell", "<u4"), ("free", "<u4"), ("n_matched", "<u4"), ("n_admitted", "<u4"),
+                               ("n_truncated", "<u4"), ("first", "<u4"), ("bytes", "<u8")])
+UDP_NONE, UDP_FULL = 0xFFFFFFFF, 0xFFFFFFFE  # port_of / cell_of of a frame no port matched / that found no free cell
+UDP_MAX_PORTS = 65536
+UDP_CELL_HEADER = 32
 # fs_tx_sock: one socket of the ring send (104 bytes, no padding), and fs_tx_sock_out (32 bytes)
 TX_SOCK_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("ring_off", "<u8"), ("ring_size", "<u4"),
                           ("ring_rpos", "<u4"), ("ring_buffered", "<u4"), ("snd_una", "<u4"), ("snd_nxt", "<u4"),
@@ -255,6 +266,24 @@ CONNECT_PROTOTYPES = {
                                           _p, _u64, _p, _p, _p, _p, _p, _p, _p]),
 }
 
+# The functions include/framesum_udp.h declares (the eighth header), in its order: product symbols too.
+# The connect call's prototypes with ports, n_ports, cells, cells_bytes, ports_out, port_of and cell_of
+# behind `reply_status`.
+UDP_PROTOTYPES = {
+    "fs_udp_flows_batch": (_st, [_p, _p, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p,
+                                 _p, _u32, _p, _u32, _u32, _p, _p, _p, _p, _p, _p,
+                                 _p, _u32, _p, _p, _p,
+                                 _p, _u32, _u32, _p, _p, _p, _p,
+                                 _p, _u32, _p, _u64, _p, _p, _p,
+                                 _p, _u64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "fs_udp_flows_batch_host": (_st, [_p, _p, _u64, _p, _p, _u32, _u32, _u32, _p, _u32, _p, _u64, _p, _p, _p, _p, _p,
+                                      _p, _u32, _p, _u32, _u32, _p, _p, _p, _p, _p, _p,
+                                      _p, _u32, _p, _p, _p,
+                                      _p, _u32, _u32, _p, _p, _p, _p,
+                                      _p, _u32, _p, _u64, _p, _p, _p,
+                                      _p, _u64, _p, _p, _p, _p, _p, _p, _p]),
+}
+
 # Not in the header, set only where the loaded library has them: the test library's hooks
 # (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
 OPTIONAL_PROTOTYPES = {
@@ -291,7 +320,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         raise FramesumError(f"{p} is missing — run __graft_entry__.build() (or make -C seqs_amd/csrc)")
     lib = ctypes.CDLL(p)
     tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **RECV_PROTOTYPES, **ACCEPT_PROTOTYPES,
-              **CLOSE_PROTOTYPES, **CONNECT_PROTOTYPES, **OPTIONAL_PROTOTYPES}
+              **CLOSE_PROTOTYPES, **CONNECT_PROTOTYPES, **UDP_PROTOTYPES, **OPTIONAL_PROTOTYPES}
     for name, (restype, argtypes) in tables.items():
         if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
             continue

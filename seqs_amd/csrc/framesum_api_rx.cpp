@@ -1,4 +1,4 @@
-// framesum C ABI -- the seven RX call kinds, each with a device form and a host form:
+// framesum C ABI -- the eight RX call kinds, each with a device form and a host form:
 //   the plain coalesce       fs_coalesce_batch, fs_coalesce_batch_host (include/framesum.h;
 //                            kernels: framesum_coalesce.hip)
 //   the flow-aware coalesce  fs_coalesce_flows_batch, ..._host (framesum_flows.hip)
@@ -15,6 +15,8 @@
 //   the connect call         fs_connect_flows_batch, ..._host (include/framesum_connect.h;
 //                            framesum_connect.hip): the close call, then the active open of every listed
 //                            opener, with the control frame it owes
+//   the UDP call             fs_udp_flows_batch, ..._host (include/framesum_udp.h; framesum_udp.hip): the
+//                            connect call, then every accepted UDP frame into its port's queue of cells
 // A call is one record (RxCall) that the entry point fills from its flat arguments; the checks, the
 // stages up to the call's kind and the one host form all read that record.
 #include <algorithm>
@@ -29,6 +31,7 @@
 #include "framesum_deliver.h"
 #include "framesum_flows.h"
 #include "framesum_recv.h"
+#include "framesum_udp.h"
 
 using namespace framesum::host;
 using framesum::RxBatch;
@@ -41,6 +44,7 @@ namespace rv = framesum::recv;
 namespace ac = framesum::accept;
 namespace cl = framesum::closing;
 namespace cn = framesum::connect;
+namespace ud = framesum::udp;
 
 namespace {
 
@@ -58,6 +62,11 @@ struct RxListen : RxList<fs_listener, framesum::RxAccept> {
 };
 using RxClosing = RxList<fs_cl_sock, framesum::RxClose>;
 using RxOpening = RxList<fs_cn_sock, framesum::RxConnect>;
+// The port list of a UDP call, with what its check makes of it (the span of `cells` the queues cover).
+struct RxPorts : RxList<fs_udp_port, framesum::RxUdp> {
+    uint64_t cells_bytes = 0;
+    ud::CheckUdp span{};
+};
 
 // The socket part of a delivery or a receive call: the caller's lists, and what check_socks makes of
 // them (the socket table, the span of `rings` the listed rings cover).
@@ -79,6 +88,7 @@ struct RxCall {
     RxListen l;
     RxClosing k;
     RxOpening o;
+    RxPorts p;
     RxCall(rxp::Kind kind_, const char* fn_, const RxBatch& b_) : kind(kind_), fn(fn_), b(b_) {}
     // the flat arguments, group by group as the ABI lists them
     void coalesce(uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, void* totals, fs_digest* out,
@@ -112,6 +122,11 @@ struct RxCall {
         o.recs = openers;
         o.dev = framesum::RxConnect{n_openers, reply_flags, openers_out, replies, reply_out, reply_status, k.dev.ctl_code};
     }
+    void datagrams(const fs_udp_port* ports, uint32_t n_ports, uint8_t* cells, uint64_t cells_bytes, fs_udp_port_out* ports_out,
+                   uint32_t* port_of, uint32_t* cell_of) {
+        p.recs = ports, p.cells_bytes = cells_bytes;
+        p.dev = framesum::RxUdp{n_ports, 0u, cells, ports_out, port_of, cell_of};
+    }
 };
 // The call as the launches see it: in the device forms the caller's batch and arrays on the caller's
 // stream, in the host forms the staged batch and the context's device arrays on the compute stream.
@@ -121,7 +136,8 @@ struct RxDevice {
     hipStream_t stream;
     framesum::RxAccept x{};  // (the accept call and the close call)
     framesum::RxClose y{};   // (the close call and the connect call)
-    framesum::RxConnect z{}; // (the connect call only)
+    framesum::RxConnect z{}; // (the connect call and the UDP call)
+    framesum::RxUdp u{};     // (the UDP call only)
 };
 
 fs_status invalid(fs_ctx* ctx, const RxCall& c, const std::string& what) {
@@ -170,7 +186,7 @@ fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
         if (cc.bad != cl::kCloseGood)
             return invalid(ctx, c, "closer " + std::to_string(cc.index) + ": " + cl::bad_close_text(cc.bad));
     }
-    if (c.kind == rxp::kConnect) {  // the opener list's checks (framesum_connect.h), which also build the table
+    if (c.kind >= rxp::kConnect) {  // the opener list's checks (framesum_connect.h), which also build the table
         RxOpening& o = c.o;
         const cn::CheckConnect co =
             cn::check_openers(o.recs, o.dev.n_openers, o.dev.reply_flags, o.dev.openers_out != nullptr, o.dev.replies != nullptr,
@@ -178,6 +194,14 @@ fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
                               ctx->flow_hash_mask, o.table);
         if (co.bad != cn::kConnectGood)
             return invalid(ctx, c, "opener " + std::to_string(co.index) + ": " + cn::bad_connect_text(co.bad));
+    }
+    if (c.kind == rxp::kUdp) {  // the port list's checks (framesum_udp.h), which also build the table
+        RxPorts& p = c.p;
+        p.span = ud::check_ports(p.recs, p.dev.n_ports, p.dev.cells != nullptr, p.dev.ports_out != nullptr, p.cells_bytes,
+                                 ctx->flow_hash_mask, p.table);
+        if (p.span.bad != ud::kUdpGood)
+            return invalid(ctx, c, "port " + std::to_string(p.span.index) + ": " + ud::bad_udp_text(p.span.bad));
+        p.dev.max_cell = ud::max_cell_size(p.recs, p.dev.n_ports);
     }
     return FS_SUCCESS;
 }
@@ -330,6 +354,26 @@ fs_status connect_stage(fs_ctx* ctx, const RxCall& c, const RxDevice& d, const R
     return staged_launch(ctx, blk.bytes, d.stream, "fs_connect_flows_batch: launch", fill, kernels);
 }
 
+// `cell_of` set to "none", and `port_of` where no port is listed (the mark launch writes every entry
+// otherwise); then, with a port listed, the ports and their table staged in a
+// block of their own and the UDP kernels (which run for an empty batch too: the out records are written).
+fs_status udp_stage(fs_ctx* ctx, const RxCall& c, const RxDevice& d, const RxLaunch& how, RxLeft& left) {
+    const framesum::RxUdp& u = d.u;
+    if (d.b.n != 0 && u.port_of && u.n_ports == 0) FS_HIP(ctx, hipMemsetAsync(u.port_of, 0xFF, 4ull * d.b.n, d.stream));
+    if (d.b.n != 0 && u.cell_of) FS_HIP(ctx, hipMemsetAsync(u.cell_of, 0xFF, 4ull * d.b.n, d.stream));
+    if (u.n_ports == 0) return FS_SUCCESS;
+    left.us = framesum::udp_scratch(d.b.n, u.n_ports);
+    if (d.b.n != 0 && left.us.sort_bytes == 0)
+        return set_err(ctx, FS_E_HIP, "fs_udp_flows_batch: the sort reports no temporary storage size");
+    const fs_status st = ctx->ud_scratch.grow(ctx, left.us.bytes);
+    if (st != FS_SUCCESS) return st;
+    left.udp_scratch = ctx->ud_scratch.p;
+    const ud::Block blk = ud::block_of(u.n_ports);
+    const auto fill = [&](uint8_t* h_block) { ud::stage(c.p.recs, u.n_ports, c.p.table.data(), blk, h_block); };
+    const auto kernels = [&](const uint8_t* d_block) { return framesum::launch_udp(d.b, d.r, u, left, d_block, how); };
+    return staged_launch(ctx, blk.bytes, d.stream, "fs_udp_flows_batch: launch", fill, kernels);
+}
+
 // The stages up to the call's kind. An empty batch has zero totals in place of its gather; the socket
 // calls still run their walks then. `left`: what the stages left (`copied`: non-empty batches only).
 fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
@@ -344,7 +388,8 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
     if (st == FS_SUCCESS && c.kind >= rxp::kRecv) st = recv_stage(ctx, c.s, d, how, left);
     if (st == FS_SUCCESS && c.kind >= rxp::kAccept) st = accept_stage(ctx, c.l, d, how, left);
     if (st == FS_SUCCESS && c.kind >= rxp::kClose) st = close_stage(ctx, c, d, how, left);
-    if (st == FS_SUCCESS && c.kind == rxp::kConnect) st = connect_stage(ctx, c, d, how, left);
+    if (st == FS_SUCCESS && c.kind >= rxp::kConnect) st = connect_stage(ctx, c, d, how, left);
+    if (st == FS_SUCCESS && c.kind == rxp::kUdp) st = udp_stage(ctx, c, d, how, left);
     return st;
 }
 
@@ -352,7 +397,7 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
 fs_status rx_device(fs_ctx* ctx, const RxCall& c, void* stream) {
     FS_HIP(ctx, hipSetDevice(ctx->device));
     RxLeft left;
-    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.dev, c.k.dev, c.o.dev}, left);
+    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.dev, c.k.dev, c.o.dev, c.p.dev}, left);
 }
 
 // ---- The own arrays of the accept, the close and the connect call in a host form, walked by
@@ -453,8 +498,11 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
             for (uint32_t i = 0; i < s.n_socks; ++i)
                 c.k.dev.socks_close[i] = cl::untouched_sock(s.socks[i].rcv_nxt, s.snd[i].snd_una, s.snd[i].snd_wnd, cl::kNone);
         }
+        if (c.kind == rxp::kUdp) {  // no port has a frame: the queues keep their state
+            for (uint32_t i = 0; i < c.p.dev.n_ports; ++i) c.p.dev.ports_out[i] = ud::port_out(c.p.recs[i], 0u);
+        }
         // no opener has a flow either, yet a flagged one owes its SYN, which only the device builds
-        if (c.kind == rxp::kConnect && c.o.dev.n_openers != 0) return connect_host_empty(ctx, c);
+        if (c.kind >= rxp::kConnect && c.o.dev.n_openers != 0) return connect_host_empty(ctx, c);
         return FS_SUCCESS;
     }
     RxExtra e(c);  // the own arrays of the accept, the close and the connect call
@@ -466,13 +514,20 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     const uint64_t span = s.span.hi - s.span.lo;
     const rxp::Layout L = rxp::layout(c.kind, n, s.n_socks);
     e.L = rxp::extra_layout(rxp::kAccept, c.kind, L.bytes, extra_counts(c));
+    // the UDP call's own arrays behind them, and the cells' span (the kernels address cells at base + cells_off)
+    const bool udp = c.kind == rxp::kUdp;
+    const framesum::RxUdp& hu = c.p.dev;
+    const rxp::UdpLayout UL = rxp::udp_layout(e.L.bytes, udp ? n : 0, udp ? hu.n_ports : 0);
+    const uint64_t cspan = c.p.span.hi - c.p.span.lo;
+    void* const h_udp[rxp::kUdpArrays] = {hu.ports_out, hu.port_of, hu.cell_of};
     fs_status st = begin_host_call(ctx);
     if (st == FS_SUCCESS && sockets) st = ctx->dl_rings.grow(ctx, span);
     // (the socket calls begin once more, behind the rings' buffer: a second hipSetDevice that keeps their
     // sequence of HIP calls what profiles/rx_call_refactor/calls.txt compares)
     if (st == FS_SUCCESS && sockets) st = begin_host_call(ctx);
     if (st == FS_SUCCESS) st = ctx->co_payload.grow(ctx, d_cap);
-    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, e.L.bytes);
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, UL.bytes);
+    if (st == FS_SUCCESS && udp) st = ctx->ud_cells.grow(ctx, cspan);
     if (st != FS_SUCCESS) return st;
     Staged sg;
     st = stage_batch(ctx, b.frames, frames_bytes, sc.lo, sc.hi, b.offsets, b.lengths, n, sg);
@@ -487,6 +542,15 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     st = extra_in(ctx, e, sg.ks);
     if (st != FS_SUCCESS) return st;
     d.x = accept_device(c.l.dev, e), d.y = close_device(c.k.dev, e), d.z = connect_device(c.o.dev, e);
+    if (udp) {
+        const auto at = [&](rxp::UdpArray a) { return h_udp[a] && UL.room[a] ? ctx->rx_arrays.p + UL.at[a] : nullptr; };
+        d.u = framesum::RxUdp{hu.n_ports, hu.max_cell, reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(ctx->ud_cells.p) - c.p.span.lo),
+                              reinterpret_cast<fs_udp_port_out*>(at(rxp::kPortsOut)), reinterpret_cast<uint32_t*>(at(rxp::kPortOf)),
+                              reinterpret_cast<uint32_t*>(at(rxp::kCellOf))};
+        // the span goes in first, so that the copy back returns the caller's own bytes around the written cells
+        if (cspan != 0)
+            FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->ud_cells.p, hu.cells + c.p.span.lo, cspan, hipMemcpyHostToDevice, sg.ks));
+    }
     RxLeft left;
     st = rx_run(ctx, c, d, left);
     if (st != FS_SUCCESS) {
@@ -517,6 +581,11 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     st = extra_back(ctx, e, sg.ks);
     if (st != FS_SUCCESS) return st;
     FS_HIP_DRAIN(ctx, back(s.n_socks ? h.rings + s.span.lo : nullptr, ctx->dl_rings.p, span));
+    if (udp) {
+        for (uint32_t a = 0; a < rxp::kUdpArrays; ++a)
+            FS_HIP_DRAIN(ctx, back(h_udp[a], ctx->rx_arrays.p + UL.at[a], UL.room[a]));
+        FS_HIP_DRAIN(ctx, back(hu.n_ports ? hu.cells + c.p.span.lo : nullptr, ctx->ud_cells.p, cspan));
+    }
     FS_HIP_DRAIN(ctx, back(h.out, sg.d_out, (uint64_t)n * sizeof(fs_digest)));
     FS_HIP_DRAIN(ctx, back(h.status, sg.d_st, n));
     st = finish_staged(ctx, sg);
@@ -526,7 +595,7 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
 
 }  // namespace
 
-// ---- The fourteen entry points: fill the record, check, run.
+// ---- The sixteen entry points: fill the record, check, run.
 
 fs_status fs_coalesce_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
                             uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
@@ -794,6 +863,68 @@ fs_status fs_connect_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64
                 synack_status);
     c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
     c.opening(openers, n_openers, reply_flags, openers_out, replies, reply_out, reply_status);
+    const fs_status st = rx_check(ctx, c, false);
+    return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
+}
+
+fs_status fs_udp_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                               uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
+                               uint8_t* rings, uint64_t rings_bytes, fs_rx_sock_out* socks_out, uint8_t* delivered,
+                               const fs_rx_snd* snd, fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                               uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots, uint32_t synack_flags,
+                               fs_accept_conn* conns, fs_listener_out* listeners_out, uint32_t* accept_of,
+                               uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status, const fs_cl_sock* closers,
+                               uint32_t n_closers, fs_cl_out* closers_out, fs_cl_out* socks_close, uint8_t* ctl_code,
+                               const fs_cn_sock* openers, uint32_t n_openers, uint32_t reply_flags, fs_cn_out* openers_out,
+                               uint8_t* replies, fs_digest* reply_out, uint8_t* reply_status,
+                               const fs_udp_port* ports, uint32_t n_ports, uint8_t* cells, uint64_t cells_bytes,
+                               fs_udp_port_out* ports_out, uint32_t* port_of, uint32_t* cell_of,
+                               uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order,
+                               uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kUdp, "fs_udp_flows_batch", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
+    c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
+    c.opening(openers, n_openers, reply_flags, openers_out, replies, reply_out, reply_status);
+    c.datagrams(ports, n_ports, cells, cells_bytes, ports_out, port_of, cell_of);
+    const fs_status st = rx_check(ctx, c, true);
+    return st != FS_SUCCESS ? st : rx_device(ctx, c, stream);
+}
+
+fs_status fs_udp_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                                    const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags,
+                                    const fs_rx_sock* socks, uint32_t n_socks, uint8_t* rings, uint64_t rings_bytes,
+                                    fs_rx_sock_out* socks_out, uint8_t* delivered, const fs_rx_snd* snd,
+                                    fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                                    uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots,
+                                    uint32_t synack_flags, fs_accept_conn* conns, fs_listener_out* listeners_out,
+                                    uint32_t* accept_of, uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status,
+                                    const fs_cl_sock* closers, uint32_t n_closers, fs_cl_out* closers_out,
+                                    fs_cl_out* socks_close, uint8_t* ctl_code, const fs_cn_sock* openers,
+                                    uint32_t n_openers, uint32_t reply_flags, fs_cn_out* openers_out, uint8_t* replies,
+                                    fs_digest* reply_out, uint8_t* reply_status, const fs_udp_port* ports, uint32_t n_ports,
+                                    uint8_t* cells, uint64_t cells_bytes, fs_udp_port_out* ports_out, uint32_t* port_of,
+                                    uint32_t* cell_of, uint8_t* payload, uint64_t payload_cap,
+                                    fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
+                                    fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kUdp, "fs_udp_flows_batch_host", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
+    c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
+    c.opening(openers, n_openers, reply_flags, openers_out, replies, reply_out, reply_status);
+    c.datagrams(ports, n_ports, cells, cells_bytes, ports_out, port_of, cell_of);
     const fs_status st = rx_check(ctx, c, false);
     return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
 }

@@ -12,6 +12,7 @@
 #include "../../include/framesum_accept.h"
 #include "../../include/framesum_close.h"
 #include "../../include/framesum_connect.h"
+#include "../../include/framesum_udp.h"
 #include "framesum_choice.h"
 #include "framesum_plan.h"
 
@@ -102,10 +103,10 @@ hipError_t launch_send_rings(const uint8_t* d_block, const segment::Block& b, ui
                              int workgroups, hipStream_t stream);
 
 // ---- The RX calls (framesum_coalesce.hip, framesum_flows.hip, framesum_deliver.hip, framesum_recv.hip,
-// framesum_accept.hip, framesum_close.hip, framesum_connect.hip). A call is a row of stages on one stream --
+// framesum_accept.hip, framesum_close.hip, framesum_connect.hip, framesum_udp.hip). A call is a row of stages on one stream --
 // the digest launch and the plain or the flow-aware gather, then the delivery, then the receive call's fold,
 // then the accept call's passive open, then the close call's control walks, then the connect call's active
-// open -- each behind the one before it and reading what it left. The launches take the call as a few records.
+// open, then the UDP call's delivery into port queues -- each behind the one before it and reading what it left. The launches take the call as a few records.
 
 // The batch as the launches read it.
 struct RxBatch {
@@ -179,6 +180,11 @@ struct OwnerScratch {
 struct ConnectScratch : OwnerScratch {
     uint64_t reprec;
 };
+// UdpScratch: 256-byte aligned like AcceptScratch (udp_scratch asks the sort for its temporary storage's
+// size too); 20 bytes per frame beside it.
+struct UdpScratch {
+    uint64_t rank_in, rank_sorted, cell_at, sort_temp, sort_bytes, bytes;
+};
 CoScratch coalesce_scratch(uint32_t n);
 FlowScratch flows_scratch(uint32_t n);
 DeliverScratch deliver_scratch(uint32_t n, uint32_t n_socks);
@@ -186,6 +192,7 @@ RecvScratch recv_scratch(uint32_t n);
 AcceptScratch accept_scratch(uint32_t n, uint32_t n_listeners, uint32_t n_slots);
 OwnerScratch owner_scratch(uint32_t n, uint32_t n_owners);
 ConnectScratch connect_scratch(uint32_t n, uint32_t n_openers);
+UdpScratch udp_scratch(uint32_t n, uint32_t n_ports);
 
 // What the accept call has beside a receive call's batch and results: the counts of its staged lists and
 // where its own results go on the device (the caller's pointers in the device form, the context's device
@@ -220,6 +227,16 @@ struct RxConnect {
     uint8_t* ctl_code;
 };
 
+// What the UDP call has beside a connect call's: the count of its list and where its own results go on
+// the device (port_of and cell_of are nullable). `cells`: the base the ports' cells_off count from.
+struct RxUdp {
+    uint32_t n_ports, max_cell;  // (max_cell: the list's largest cell_size, which decides the copy's lanes)
+    uint8_t* cells;
+    fs_udp_port_out* ports_out;
+    uint32_t* port_of;
+    uint32_t* cell_of;
+};
+
 // What the stages of one call leave on the device for the stages behind them: each stage's scratch, laid
 // out as its layout says (all zero for a stage that has not run: an empty batch has no flow stage), and
 // where the gather's count of written payload bytes lies.
@@ -237,6 +254,8 @@ struct RxLeft {
     OwnerScratch cs;
     uint8_t* connect_scratch;
     ConnectScratch cns;
+    uint8_t* udp_scratch;
+    UdpScratch us;
 };
 
 // The launches that follow a batch's digest launch on the stream (fs_coalesce_batch in
@@ -286,5 +305,12 @@ void launch_flow_gather_sq(const RxBatch& b, const RxLeft& left, uint8_t* scratc
 // launch_accept's, for the reply kernel. With n of 0 only the out records and the flagged SYNs are written.
 hipError_t launch_connect(const RxBatch& b, const RxResults& r, const RxConnect& z, const RxLeft& left, const uint8_t* d_block,
                           const SegTables* tables, int tx_workgroups, const RxLaunch& how);
+
+// The launches that follow a batch's connect launches (fs_udp_flows_batch in include/framesum_udp.h) and
+// read the verdicts and, when every step of the flow launches ran, the key records those left. `d_block`:
+// the device copy of the staged block (framesum_udp.h block_of: the ports, then their table); at least one
+// port. With n of 0 only the out records are written.
+hipError_t launch_udp(const RxBatch& b, const RxResults& r, const RxUdp& u, const RxLeft& left, const uint8_t* d_block,
+                      const RxLaunch& how);
 
 }  // namespace framesum

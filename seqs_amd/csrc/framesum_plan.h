@@ -217,7 +217,7 @@ inline void host_chunks(const uint64_t* offsets, const uint32_t* lengths, uint32
 }
 
 // ---------------------------------------------------------------------------------------
-// The device result arrays of the seven RX host forms (fs_coalesce_batch_host,
+// The device result arrays of the first seven RX host forms (fs_coalesce_batch_host,
 // fs_coalesce_flows_batch_host, fs_deliver_flows_batch_host, fs_recv_flows_batch_host and, with the
 // arrays of their own in the second table below, fs_accept_flows_batch_host,
 // fs_close_flows_batch_host and fs_connect_flows_batch_host), described
@@ -227,7 +227,7 @@ inline void host_chunks(const uint64_t* offsets, const uint32_t* lengths, uint32
 namespace rx {
 
 // A kind has the arrays of the kinds before it and its own.
-enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv, kAccept, kClose, kConnect };
+enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv, kAccept, kClose, kConnect, kUdp };
 enum Array : uint32_t { kTotals, kRuns, kFlowRecs, kOrder, kRunOf, kDelivered, kSocksOut, kSndOut, kCode, kArrays };
 // What counts an array's entries: one record, the batch's frames, the call's sockets, or (for what
 // comes back only) one of the totals.
@@ -347,6 +347,38 @@ inline ExtraLayout extra_layout(Kind first, Kind last, uint64_t base, const Extr
         at = (at + d.align - 1) / d.align * d.align;
         L.at[a] = at;
         L.room[a] = d.elem * counts.of[d.count];
+        at += L.room[a];
+    }
+    L.bytes = at;
+    return L;
+}
+
+// The own arrays of the eighth kind (fs_udp_flows_batch_host), in a description of their own: they lie
+// behind extra_layout(kAccept, kConnect, ...)'s rows in the same buffer, in this order, every entry is
+// written by the call and every array comes back whole. (`cells` is no such array: the span of it that
+// the listed queues cover has a buffer of its own, as the rings have.)
+enum UdpArray : uint32_t { kPortsOut, kPortOf, kCellOf, kUdpArrays };
+enum UdpCount : uint32_t { kPerPort, kPerUdpFrame };
+struct UdpArrayDesc {
+    uint32_t elem, align;  // bytes per entry, and the alignment the kernels' stores want
+    UdpCount count;
+};
+constexpr UdpArrayDesc kUdpArrayDesc[kUdpArrays] = {
+    {32, 8, kPerPort},      // fs_udp_port_out (its `bytes` is a 64-bit sum)
+    {4, 4, kPerUdpFrame},   // port_of
+    {4, 4, kPerUdpFrame},   // cell_of
+};
+struct UdpLayout {
+    uint64_t at[kUdpArrays], room[kUdpArrays], bytes;  // `bytes`: `base` and the rows laid out
+};
+inline UdpLayout udp_layout(uint64_t base, uint64_t n, uint64_t n_ports) {
+    UdpLayout L;
+    uint64_t at = base;
+    for (uint32_t a = 0; a < kUdpArrays; ++a) {
+        const UdpArrayDesc& d = kUdpArrayDesc[a];
+        at = (at + d.align - 1) / d.align * d.align;
+        L.at[a] = at;
+        L.room[a] = d.elem * (d.count == kPerPort ? n_ports : n);
         at += L.room[a];
     }
     L.bytes = at;

@@ -34,6 +34,7 @@ from .abi import (  # noqa: F401 (re-exported: this module is the binding's publ
     RECV_RING_FULL, RECV_TAKEN, RECV_UNSENT, RUN_DTYPE, RX_FCS, SEGMENT_MAX_FRAMES, SEND_DTYPE, SEND_MAX_SOCKS, SEND_NONE,
     SEND_RINGS_PROTOTYPES, SND_DTYPE, SND_OUT_DTYPE, SOCK_DTYPE, SOCK_OUT_DTYPE, TEST_LIB_PATH, TOTALS_DTYPE, TX_ACK, TX_FIN,
     TX_PSH, TX_SOCK_DTYPE, TX_SOCK_OUT_DTYPE, VERDICTS, FramesumError, lib_path, load_library, sock_key,
+    UDP_CELL_DTYPE, UDP_CELL_HEADER, UDP_FULL, UDP_MAX_PORTS, UDP_NONE, UDP_PORT_DTYPE, UDP_PORT_OUT_DTYPE, UDP_PROTOTYPES,
 )
 
 _vp, _u64 = ctypes.c_void_p, ctypes.c_uint64
@@ -93,6 +94,7 @@ _RX_RECV = ("fs_recv_flows_batch", *_RX_FLOWS[1:])  # (the delivery call with sn
 _RX_ACCEPT = ("fs_accept_flows_batch", *_RX_FLOWS[1:])  # (the receive call with the listening arguments behind code)
 _RX_CLOSE = ("fs_close_flows_batch", *_RX_FLOWS[1:])  # (the accept call with the closing arguments behind synack_status)
 _RX_CONNECT = ("fs_connect_flows_batch", *_RX_FLOWS[1:])  # (the close call with the opening arguments behind ctl_code)
+_RX_UDP = ("fs_udp_flows_batch", *_RX_FLOWS[1:])  # (the connect call with the port arguments behind reply_status)
 
 
 @dataclass
@@ -641,6 +643,15 @@ class Engine(_Handle):
                 rep_st = torch.zeros((n_open,), dtype=torch.uint8, device=dev) if reply_results else None
                 args += (_array_ptr(openers), n_open, reply_flags, ptr(openers_out), ptr(replies), ptr(rep_out), ptr(rep_st))
                 rx, mine = _RX_CONNECT, (openers_out, replies, rep_out, rep_st, *mine)
+                if len(_closing) > 3:  # udp_flows_device: the port arguments behind reply_status, its tensors in front
+                    ports, cells, want_port_of, want_cell_of = _closing[3]
+                    assert cells.is_cuda and cells.dtype == torch.uint8 and cells.is_contiguous()
+                    ports_out = torch.empty((int(ports.size), UDP_PORT_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                    port_of = torch.empty((n,), dtype=torch.int32, device=dev) if want_port_of else None
+                    cell_of = torch.empty((n,), dtype=torch.int32, device=dev) if want_cell_of else None
+                    args += (_array_ptr(ports), int(ports.size), ptr(cells), cells.numel(), ptr(ports_out), ptr(port_of),
+                             ptr(cell_of))
+                    rx, mine = _RX_UDP, (ports_out, port_of, cell_of, *mine)
         return (*mine, conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
                 *self._rx_device(rx, frames, offsets, lengths, mtu, flags, payload, stream, args))
 
@@ -709,6 +720,16 @@ class Engine(_Handle):
                 rep_st = np.zeros(n_open, dtype=np.uint8) if reply_results else None
                 args += (_array_ptr(openers), n_open, reply_flags, ptr(openers_out), ptr(replies), ptr(rep_out), ptr(rep_st))
                 rx, mine = _RX_CONNECT, (openers_out, replies, rep_out, rep_st, *mine)
+                if len(_closing) > 3:  # udp_flows_host
+                    ports, cells, want_port_of, want_cell_of = _closing[3]
+                    assert isinstance(cells, np.ndarray) and cells.dtype == np.uint8 and cells.flags["C_CONTIGUOUS"]
+                    assert cells.flags["WRITEABLE"], "udp_flows_host writes into `cells`"
+                    ports_out = np.zeros(int(ports.size), dtype=UDP_PORT_OUT_DTYPE)
+                    port_of = np.full(n, UDP_NONE, dtype=np.uint32) if want_port_of else None
+                    cell_of = np.full(n, UDP_NONE, dtype=np.uint32) if want_cell_of else None
+                    args += (_array_ptr(ports), int(ports.size), ptr(cells), cells.nbytes, ptr(ports_out), ptr(port_of),
+                             ptr(cell_of))
+                    rx, mine = _RX_UDP, (ports_out, port_of, cell_of, *mine)
         return (*mine, conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
                 *self._rx_host(rx, frames, offsets, lengths, mtu, flags, payload, args))
 
@@ -773,6 +794,41 @@ class Engine(_Handle):
         openers = np.ascontiguousarray(openers, dtype=OPENER_DTYPE)
         return self.accept_flows_host(frames, offsets, lengths, socks, snd, rings, listeners, slots,
                                       _closing=(closers, ctl_code, (openers, reply_flags, replies, reply_results)), **kw)
+
+    # ---- the UDP call: the connect call plus the datagrams' delivery into port queues (include/framesum_udp.h) ----
+    def udp_flows_device(self, frames, offsets, lengths, socks: np.ndarray, snd: np.ndarray, rings,
+                         listeners: np.ndarray, slots: np.ndarray, closers: np.ndarray, openers: np.ndarray,
+                         ports: np.ndarray, cells, port_of: bool = True, cell_of: bool = True, reply_flags: int = 0,
+                         replies=None, reply_results: bool = True, ctl_code: bool = True, **kw):
+        """connect_flows_device plus the UDP half of RecvEth (fs_udp_flows_batch): `ports` is a UDP_PORT_DTYPE
+        array on the host (udp_port() makes one row), `cells` the uint8 CUDA tensor the ports' queues lie in.
+        Every accepted UDP frame whose destination a port lists goes to the port's next free cell, in batch
+        order: a 32-byte UDP_CELL_DTYPE header, then the payload, cut to the cell's room. Further keyword
+        arguments are accept_flows_device's. Returns (ports_out, port_of, cell_of, then connect_flows_device's
+        tuple) device tensors: ports_out (n_ports, 32) uint8 = UDP_PORT_OUT_DTYPE records, port_of and cell_of
+        (n,) int32 (-1 = UDP_NONE, -2 = UDP_FULL; None when the flag is False). Asynchronous on `stream`;
+        split_dgrams() brings the datagrams to the host."""
+        closers = np.ascontiguousarray(closers, dtype=CLOSER_DTYPE)
+        openers = np.ascontiguousarray(openers, dtype=OPENER_DTYPE)
+        ports = np.ascontiguousarray(ports, dtype=UDP_PORT_DTYPE)
+        return self.accept_flows_device(frames, offsets, lengths, socks, snd, rings, listeners, slots,
+                                        _closing=(closers, ctl_code, (openers, reply_flags, replies, reply_results),
+                                                  (ports, cells, port_of, cell_of)), **kw)
+
+    def udp_flows_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, socks: np.ndarray,
+                       snd: np.ndarray, rings: np.ndarray, listeners: np.ndarray, slots: np.ndarray, closers: np.ndarray,
+                       openers: np.ndarray, ports: np.ndarray, cells: np.ndarray, port_of: bool = True, cell_of: bool = True,
+                       reply_flags: int = 0, replies=None, reply_results: bool = True, ctl_code: bool = True, **kw):
+        """udp_flows_device from and to host memory (fs_udp_flows_batch_host). `cells`: a writable uint8
+        array, written in place in the cells that take a datagram. Returns (ports_out
+        UDP_PORT_OUT_DTYPE[n_ports], port_of uint32[n] or None, cell_of uint32[n] or None, then
+        connect_flows_host's tuple)."""
+        closers = np.ascontiguousarray(closers, dtype=CLOSER_DTYPE)
+        openers = np.ascontiguousarray(openers, dtype=OPENER_DTYPE)
+        ports = np.ascontiguousarray(ports, dtype=UDP_PORT_DTYPE)
+        return self.accept_flows_host(frames, offsets, lengths, socks, snd, rings, listeners, slots,
+                                      _closing=(closers, ctl_code, (openers, reply_flags, replies, reply_results),
+                                                (ports, cells, port_of, cell_of)), **kw)
 
     # ---- TCP segments from socket TX rings (include/framesum_send.h) ------------
     @staticmethod
@@ -993,7 +1049,9 @@ def tx_sock_from(sock_out, tx=None, snd_out=None, **fields) -> np.ndarray:
 
 
 def _records(t, dtype) -> np.ndarray:
-    """A device tensor of records (or of uint32 held as int32) as a host array of `dtype`."""
+    """A device tensor of records (or of uint32 held as int32) as a host array of `dtype`; a host array as it is."""
+    if isinstance(t, np.ndarray):
+        return np.ascontiguousarray(t).reshape(-1).view(dtype)
     return np.ascontiguousarray(t.cpu().numpy()).reshape(-1).view(dtype)
 
 
@@ -1044,6 +1102,52 @@ def split_connect(openers_out, reply_out=None, reply_status=None):
     None)."""
     return (_records(openers_out, CONNECT_OUT_DTYPE), None if reply_out is None else _records(reply_out, DIGEST_DTYPE),
             None if reply_status is None else _records(reply_status, np.uint8))
+
+
+def udp_port(local_ip, local_port: int, n_cells: int, cell_size: int, cells_off: int = 0, wcell: int = 0, free=None):
+    """One UDP_PORT_DTYPE row: a port that takes the datagrams to `local_ip` (4 bytes, a dotted string or
+    an integer; 0.0.0.0: any destination address) and `local_port`, with a queue of `n_cells` cells of
+    `cell_size` bytes at `cells_off`. `free`: the cells the consumer has handed back (all of them unless
+    given)."""
+    row = np.zeros(1, dtype=UDP_PORT_DTYPE)
+    row["local"][0] = sock_key(0, 0, local_ip, local_port)[[5, 6, 7, 8, 11, 12]]
+    row["n_cells"], row["cell_size"], row["cells_off"], row["wcell"] = n_cells, cell_size, cells_off, wcell
+    row["free"] = n_cells if free is None else free
+    return row
+
+
+def split_dgrams(cells, ports, ports_out):
+    """The datagrams a UDP call admitted, per port in arrival order: a list (one entry per port) of lists of
+    (header, payload) with `header` one UDP_CELL_DTYPE record and `payload` its `stored` bytes. `cells`: the
+    call's uint8 tensor or array (a tensor is waited for and brought to the host), `ports` the rows the call
+    was given, `ports_out` its records."""
+    cells = _records(cells, np.uint8).reshape(-1)
+    ports = np.atleast_1d(np.asarray(ports, dtype=UDP_PORT_DTYPE))
+    outs = np.atleast_1d(_records(ports_out, UDP_PORT_OUT_DTYPE))
+    assert ports.size == outs.size, "one out record per port"
+    res = []
+    for p, o in zip(ports, outs):
+        got = []
+        for r in range(int(o["n_admitted"])):
+            at = int(p["cells_off"]) + ((int(p["wcell"]) + r) % int(p["n_cells"])) * int(p["cell_size"])
+            h = cells[at : at + UDP_CELL_HEADER].view(UDP_CELL_DTYPE)[0]
+            got.append((h, bytes(cells[at + UDP_CELL_HEADER : at + UDP_CELL_HEADER + int(h["stored"])])))
+        res.append(got)
+    return res
+
+
+def ports_after(ports, ports_out, consumed=None):
+    """The port list for the next call: `ports` with the state `ports_out` reports, and `consumed` cells per
+    port (one number for all, or an array; every admitted datagram unless given) handed back."""
+    nxt = np.atleast_1d(np.asarray(ports, dtype=UDP_PORT_DTYPE)).copy()
+    outs = np.atleast_1d(_records(ports_out, UDP_PORT_OUT_DTYPE))
+    assert nxt.size == outs.size, "one out record per port"
+    nxt["wcell"] = outs["wcell"]
+    free = outs["free"].astype(np.uint64) + (np.asarray(consumed, dtype=np.uint64) if consumed is not None
+                                             else outs["n_admitted"].astype(np.uint64))
+    assert (free <= nxt["n_cells"]).all(), "more cells handed back than the queue has in use"
+    nxt["free"] = free
+    return nxt
 
 
 def socks_from_connect(openers, out, ring_off=0, ring_size=0, mss: int = 1460):
