@@ -125,6 +125,19 @@ UDP_PORT_OUT_DTYPE = np.dtype([("wcell", "<u4"), ("free", "<u4"), ("n_matched", 
 UDP_NONE, UDP_FULL = 0xFFFFFFFF, 0xFFFFFFFE  # port_of / cell_of of a frame no port matched / that found no free cell
 UDP_MAX_PORTS = 65536
 UDP_CELL_HEADER = 32
+# The ARP call (include/framesum_arp.h): fs_arp_host (20 bytes), fs_arp_query (12), fs_arp_host_out (16) and
+# fs_arp_query_out (16), none with padding
+ARP_HOST_DTYPE = np.dtype([("ip", "u1", (4,)), ("mac", "u1", (6,)), ("reserved", "<u2"), ("slot0", "<u4"), ("free", "<u4")])
+ARP_QUERY_DTYPE = np.dtype([("host", "<u4"), ("target", "u1", (4,)), ("flags", "<u2"), ("reserved", "<u2")])
+ARP_HOST_OUT_DTYPE = np.dtype([("n_requests", "<u4"), ("n_answered", "<u4"), ("first", "<u4"), ("free", "<u4")])
+ARP_QUERY_OUT_DTYPE = np.dtype([("state", "u1"), ("reserved", "u1"), ("mac", "u1", (6,)), ("frame", "<u4"), ("n_replies", "<u4")])
+ARP_NONE = 0xFFFFFFFF  # arp_of of a frame with no slot and no query; `first` and `frame` without a frame
+ARP_MAX_HOSTS = ARP_MAX_QUERIES = ARP_MAX_REPLY_SLOTS = 65536
+ARP_FRAME, ARP_FRAME_PADDED = 42, 60
+ARP_PAD = 1  # arp_flags, beside FCS_APPEND
+ARP_SEND_REQUEST = 1  # fs_arp_query.flags
+ARP_NOT_ARP, ARP_UNSUPPORTED, ARP_IGNORED, ARP_ANSWERED, ARP_FULL, ARP_RESOLVED, ARP_STALE = range(7)  # arp_code
+ARP_Q_WAIT, ARP_Q_DONE, ARP_Q_SENT = range(3)  # fs_arp_query_out.state
 # fs_tx_sock: one socket of the ring send (104 bytes, no padding), and fs_tx_sock_out (32 bytes)
 TX_SOCK_DTYPE = np.dtype([("hdr", "u1", (54,)), ("mss", "<u2"), ("ring_off", "<u8"), ("ring_size", "<u4"),
                           ("ring_rpos", "<u4"), ("ring_buffered", "<u4"), ("snd_una", "<u4"), ("snd_nxt", "<u4"),
@@ -284,6 +297,17 @@ UDP_PROTOTYPES = {
                                       _p, _u64, _p, _p, _p, _p, _p, _p, _p]),
 }
 
+# The functions include/framesum_arp.h declares (the ninth header), in its order: product symbols too.
+# The UDP call's prototypes with hosts, n_hosts, queries, n_queries, n_reply_slots, arp_flags, hosts_out,
+# queries_out, arp_frames, arp_out, arp_status, arp_code and arp_of behind `cell_of`.
+_ARP_ARGS = [_p, _u32, _p, _u32, _u32, _u32, _p, _p, _p, _p, _p, _p, _p]
+ARP_PROTOTYPES = {
+    "fs_arp_flows_batch": (_st, UDP_PROTOTYPES["fs_udp_flows_batch"][1][:46] + _ARP_ARGS
+                           + UDP_PROTOTYPES["fs_udp_flows_batch"][1][46:]),
+    "fs_arp_flows_batch_host": (_st, UDP_PROTOTYPES["fs_udp_flows_batch_host"][1][:47] + _ARP_ARGS
+                                + UDP_PROTOTYPES["fs_udp_flows_batch_host"][1][47:]),
+}
+
 # Not in the header, set only where the loaded library has them: the test library's hooks
 # (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
 OPTIONAL_PROTOTYPES = {
@@ -320,7 +344,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         raise FramesumError(f"{p} is missing — run __graft_entry__.build() (or make -C seqs_amd/csrc)")
     lib = ctypes.CDLL(p)
     tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **RECV_PROTOTYPES, **ACCEPT_PROTOTYPES,
-              **CLOSE_PROTOTYPES, **CONNECT_PROTOTYPES, **UDP_PROTOTYPES, **OPTIONAL_PROTOTYPES}
+              **CLOSE_PROTOTYPES, **CONNECT_PROTOTYPES, **UDP_PROTOTYPES, **ARP_PROTOTYPES,
+              **OPTIONAL_PROTOTYPES}
     for name, (restype, argtypes) in tables.items():
         if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
             continue

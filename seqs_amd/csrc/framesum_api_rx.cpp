@@ -1,4 +1,4 @@
-// framesum C ABI -- the eight RX call kinds, each with a device form and a host form:
+// framesum C ABI -- the nine RX call kinds, each with a device form and a host form:
 //   the plain coalesce       fs_coalesce_batch, fs_coalesce_batch_host (include/framesum.h;
 //                            kernels: framesum_coalesce.hip)
 //   the flow-aware coalesce  fs_coalesce_flows_batch, ..._host (framesum_flows.hip)
@@ -17,6 +17,8 @@
 //                            opener, with the control frame it owes
 //   the UDP call             fs_udp_flows_batch, ..._host (include/framesum_udp.h; framesum_udp.hip): the
 //                            connect call, then every accepted UDP frame into its port's queue of cells
+//   the ARP call             fs_arp_flows_batch, ..._host (include/framesum_arp.h; framesum_arp.hip): the
+//                            UDP call, then every ARP request answered and every ARP reply matched
 // A call is one record (RxCall) that the entry point fills from its flat arguments; the checks, the
 // stages up to the call's kind and the one host form all read that record.
 #include <algorithm>
@@ -32,6 +34,7 @@
 #include "framesum_flows.h"
 #include "framesum_recv.h"
 #include "framesum_udp.h"
+#include "framesum_arp.h"
 
 using namespace framesum::host;
 using framesum::RxBatch;
@@ -45,6 +48,7 @@ namespace ac = framesum::accept;
 namespace cl = framesum::closing;
 namespace cn = framesum::connect;
 namespace ud = framesum::udp;
+namespace ar = framesum::arp;
 
 namespace {
 
@@ -68,6 +72,14 @@ struct RxPorts : RxList<fs_udp_port, framesum::RxUdp> {
     ud::CheckUdp span{};
 };
 
+// The host and query lists of an ARP call, with what their check builds (the key records and the tables).
+struct RxNeighbours {
+    const fs_arp_host* hosts = nullptr;
+    const fs_arp_query* queries = nullptr;
+    framesum::RxArp dev{};
+    ar::Built built;
+};
+
 // The socket part of a delivery or a receive call: the caller's lists, and what check_socks makes of
 // them (the socket table, the span of `rings` the listed rings cover).
 struct RxSocks {
@@ -89,6 +101,7 @@ struct RxCall {
     RxClosing k;
     RxOpening o;
     RxPorts p;
+    RxNeighbours a;
     RxCall(rxp::Kind kind_, const char* fn_, const RxBatch& b_) : kind(kind_), fn(fn_), b(b_) {}
     // the flat arguments, group by group as the ABI lists them
     void coalesce(uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, uint32_t* run_of, void* totals, fs_digest* out,
@@ -127,6 +140,13 @@ struct RxCall {
         p.recs = ports, p.cells_bytes = cells_bytes;
         p.dev = framesum::RxUdp{n_ports, 0u, cells, ports_out, port_of, cell_of};
     }
+    void neighbours(const fs_arp_host* hosts, uint32_t n_hosts, const fs_arp_query* queries, uint32_t n_queries,
+                    uint32_t n_reply_slots, uint32_t arp_flags, fs_arp_host_out* hosts_out, fs_arp_query_out* queries_out,
+                    uint8_t* arp_frames, fs_digest* arp_out, uint8_t* arp_status, uint8_t* arp_code, uint32_t* arp_of) {
+        a.hosts = hosts, a.queries = queries;
+        a.dev = framesum::RxArp{n_hosts,    n_queries, n_reply_slots, arp_flags, hosts_out, queries_out,
+                                arp_frames, arp_out,   arp_status,    arp_code,  arp_of};
+    }
 };
 // The call as the launches see it: in the device forms the caller's batch and arrays on the caller's
 // stream, in the host forms the staged batch and the context's device arrays on the compute stream.
@@ -137,7 +157,8 @@ struct RxDevice {
     framesum::RxAccept x{};  // (the accept call and the close call)
     framesum::RxClose y{};   // (the close call and the connect call)
     framesum::RxConnect z{}; // (the connect call and the UDP call)
-    framesum::RxUdp u{};     // (the UDP call only)
+    framesum::RxUdp u{};     // (the UDP call and the ARP call)
+    framesum::RxArp w{};     // (the ARP call only)
 };
 
 fs_status invalid(fs_ctx* ctx, const RxCall& c, const std::string& what) {
@@ -195,13 +216,21 @@ fs_status rx_check(fs_ctx* ctx, RxCall& c, bool aligned) {
         if (co.bad != cn::kConnectGood)
             return invalid(ctx, c, "opener " + std::to_string(co.index) + ": " + cn::bad_connect_text(co.bad));
     }
-    if (c.kind == rxp::kUdp) {  // the port list's checks (framesum_udp.h), which also build the table
+    if (c.kind >= rxp::kUdp) {  // the port list's checks (framesum_udp.h), which also build the table
         RxPorts& p = c.p;
         p.span = ud::check_ports(p.recs, p.dev.n_ports, p.dev.cells != nullptr, p.dev.ports_out != nullptr, p.cells_bytes,
                                  ctx->flow_hash_mask, p.table);
         if (p.span.bad != ud::kUdpGood)
             return invalid(ctx, c, "port " + std::to_string(p.span.index) + ": " + ud::bad_udp_text(p.span.bad));
         p.dev.max_cell = ud::max_cell_size(p.recs, p.dev.n_ports);
+    }
+    if (c.kind == rxp::kArp) {  // the host and query lists' checks (framesum_arp.h), which also build the tables
+        RxNeighbours& a = c.a;
+        const ar::CheckArp ca = ar::check_arp(a.hosts, a.dev.n_hosts, a.queries, a.dev.n_queries, a.dev.n_reply_slots,
+                                              a.dev.arp_flags, a.dev.hosts_out != nullptr, a.dev.queries_out != nullptr,
+                                              a.dev.arp_frames != nullptr, ctx->flow_hash_mask, a.built);
+        if (ca.bad != ar::kArpGood)
+            return invalid(ctx, c, "host or query " + std::to_string(ca.index) + ": " + ar::bad_arp_text(ca.bad));
     }
     return FS_SUCCESS;
 }
@@ -374,6 +403,31 @@ fs_status udp_stage(fs_ctx* ctx, const RxCall& c, const RxDevice& d, const RxLau
     return staged_launch(ctx, blk.bytes, d.stream, "fs_udp_flows_batch: launch", fill, kernels);
 }
 
+// With a host listed: the hosts, the queries and their tables staged in a block of their own and the ARP
+// kernels (which run for an empty batch too: the out records and the flagged requests are written). With
+// none: the one launch that writes `arp_code` and `arp_of`, where given.
+fs_status arp_stage(fs_ctx* ctx, const RxCall& c, const RxDevice& d, const RxLaunch& how, RxLeft& left) {
+    const framesum::RxArp& w = d.w;
+    if (w.n_hosts == 0) {
+        if (d.b.n == 0 || (!w.arp_code && !w.arp_of)) return FS_SUCCESS;
+        FS_HIP(ctx, framesum::launch_arp(d.b, d.r, w, left, nullptr, nullptr, 0, how));
+        return FS_SUCCESS;
+    }
+    left.ars = framesum::arp_scratch(d.b.n, w.n_hosts, w.n_queries, w.n_reply_slots);
+    if (d.b.n != 0 && left.ars.sort_bytes == 0)
+        return set_err(ctx, FS_E_HIP, "fs_arp_flows_batch: the sort reports no temporary storage size");
+    fs_status st = ctx->ar_scratch.grow(ctx, left.ars.bytes);
+    if (st == FS_SUCCESS) st = seg_tables(ctx);
+    if (st != FS_SUCCESS) return st;
+    left.arp_scratch = ctx->ar_scratch.p;
+    const ar::Block blk = ar::block_of(w.n_hosts, w.n_queries);
+    const auto fill = [&](uint8_t* h_block) { ar::stage(c.a.hosts, w.n_hosts, c.a.queries, w.n_queries, c.a.built, blk, h_block); };
+    const auto kernels = [&](const uint8_t* d_block) {
+        return framesum::launch_arp(d.b, d.r, w, left, d_block, ctx->d_seg_tables, tx_workgroups(ctx), how);
+    };
+    return staged_launch(ctx, blk.bytes, d.stream, "fs_arp_flows_batch: launch", fill, kernels);
+}
+
 // The stages up to the call's kind. An empty batch has zero totals in place of its gather; the socket
 // calls still run their walks then. `left`: what the stages left (`copied`: non-empty batches only).
 fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
@@ -389,7 +443,8 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
     if (st == FS_SUCCESS && c.kind >= rxp::kAccept) st = accept_stage(ctx, c.l, d, how, left);
     if (st == FS_SUCCESS && c.kind >= rxp::kClose) st = close_stage(ctx, c, d, how, left);
     if (st == FS_SUCCESS && c.kind >= rxp::kConnect) st = connect_stage(ctx, c, d, how, left);
-    if (st == FS_SUCCESS && c.kind == rxp::kUdp) st = udp_stage(ctx, c, d, how, left);
+    if (st == FS_SUCCESS && c.kind >= rxp::kUdp) st = udp_stage(ctx, c, d, how, left);
+    if (st == FS_SUCCESS && c.kind == rxp::kArp) st = arp_stage(ctx, c, d, how, left);
     return st;
 }
 
@@ -397,7 +452,8 @@ fs_status rx_run(fs_ctx* ctx, const RxCall& c, RxDevice d, RxLeft& left) {
 fs_status rx_device(fs_ctx* ctx, const RxCall& c, void* stream) {
     FS_HIP(ctx, hipSetDevice(ctx->device));
     RxLeft left;
-    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.dev, c.k.dev, c.o.dev, c.p.dev}, left);
+    return rx_run(ctx, c, RxDevice{c.b, c.r, reinterpret_cast<hipStream_t>(stream), c.l.dev, c.k.dev, c.o.dev, c.p.dev, c.a.dev},
+                  left);
 }
 
 // ---- The own arrays of the accept, the close and the connect call in a host form, walked by
@@ -475,6 +531,67 @@ fs_status connect_host_empty(fs_ctx* ctx, const RxCall& c) {
     return FS_SUCCESS;
 }
 
+// ---- The own arrays of the ARP call in a host form, walked by plan::rx::kArpArrayDesc.
+struct RxArpArrays {
+    void* h[rxp::kArpArrays];
+    void* d[rxp::kArpArrays] = {};
+    rxp::ArpLayout L{};
+    explicit RxArpArrays(const framesum::RxArp& w)
+        : h{w.hosts_out, w.queries_out, w.arp_frames, w.arp_out, w.arp_status, w.arp_code, w.arp_of} {}
+    template <class T>
+    T* as(rxp::ArpArray a) const { return static_cast<T*>(d[a]); }
+};
+rxp::ArpCounts arp_counts(const framesum::RxArp& w, uint64_t n) {
+    return rxp::ArpCounts{{w.n_hosts, w.n_queries, (uint64_t)w.n_reply_slots + w.n_queries, n}};
+}
+fs_status arp_in(fs_ctx* ctx, RxArpArrays& e, hipStream_t ks) {
+    for (uint32_t a = 0; a < rxp::kArpArrays; ++a) {
+        if (!e.h[a] || e.L.room[a] == 0) continue;
+        e.d[a] = ctx->rx_arrays.p + e.L.at[a];
+        if (rxp::kArpArrayDesc[a].goes_in) FS_HIP_DRAIN(ctx, hipMemcpyAsync(e.d[a], e.h[a], e.L.room[a], hipMemcpyHostToDevice, ks));
+    }
+    return FS_SUCCESS;
+}
+fs_status arp_back(fs_ctx* ctx, const RxArpArrays& e, hipStream_t ks) {
+    for (uint32_t a = 0; a < rxp::kArpArrays; ++a)
+        if (e.d[a]) FS_HIP_DRAIN(ctx, hipMemcpyAsync(e.h[a], e.d[a], e.L.room[a], hipMemcpyDeviceToHost, ks));
+    return FS_SUCCESS;
+}
+framesum::RxArp arp_device(const framesum::RxArp& hw, const RxArpArrays& e) {
+    return framesum::RxArp{hw.n_hosts, hw.n_queries, hw.n_reply_slots, hw.arp_flags, e.as<fs_arp_host_out>(rxp::kHostsOut),
+                           e.as<fs_arp_query_out>(rxp::kQueriesOut), e.as<uint8_t>(rxp::kArpFrames), e.as<fs_digest>(rxp::kArpOut),
+                           e.as<uint8_t>(rxp::kArpStatus), e.as<uint8_t>(rxp::kArpCode), e.as<uint32_t>(rxp::kArpOf)};
+}
+
+// The ARP call's host form without a batch, as connect_host_empty: nothing is staged but the hosts and the
+// queries; the ARP stage alone runs on the compute stream over the context's device arrays (a flagged query
+// owes its request, which only the device builds), and its arrays come back.
+fs_status arp_host_empty(fs_ctx* ctx, const RxCall& c) {
+    RxArpArrays e(c.a.dev);
+    e.L = rxp::arp_layout(0, arp_counts(c.a.dev, 0));
+    fs_status st = begin_host_call(ctx);
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, e.L.bytes);
+    if (st != FS_SUCCESS) return st;
+    const hipStream_t ks = ctx->compute_stream;
+    ctx->host_dirty = true;
+    st = arp_in(ctx, e, ks);
+    if (st != FS_SUCCESS) return st;
+    RxDevice d{c.b, RxResults{}, ks};
+    d.w = arp_device(c.a.dev, e);
+    const RxLaunch how{rx_workgroups(ctx), ctx->flow_hash_mask, ctx->flow_steps, ks};
+    RxLeft left{};
+    st = arp_stage(ctx, c, d, how, left);
+    if (st != FS_SUCCESS) {
+        drain_host_streams(ctx);
+        return st;
+    }
+    st = arp_back(ctx, e, ks);
+    if (st != FS_SUCCESS) return st;
+    FS_HIP_DRAIN(ctx, hipStreamSynchronize(ks));
+    ctx->host_dirty = false;
+    return FS_SUCCESS;
+}
+
 // A checked host form: the batch staged through slot 0, the result arrays carved from the context's
 // buffer as plan::rx::layout and extra_layout say, the stages, then what they wrote copied back by the same description.
 fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
@@ -498,11 +615,16 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
             for (uint32_t i = 0; i < s.n_socks; ++i)
                 c.k.dev.socks_close[i] = cl::untouched_sock(s.socks[i].rcv_nxt, s.snd[i].snd_una, s.snd[i].snd_wnd, cl::kNone);
         }
-        if (c.kind == rxp::kUdp) {  // no port has a frame: the queues keep their state
+        if (c.kind >= rxp::kUdp) {  // no port has a frame: the queues keep their state
             for (uint32_t i = 0; i < c.p.dev.n_ports; ++i) c.p.dev.ports_out[i] = ud::port_out(c.p.recs[i], 0u);
         }
         // no opener has a flow either, yet a flagged one owes its SYN, which only the device builds
-        if (c.kind >= rxp::kConnect && c.o.dev.n_openers != 0) return connect_host_empty(ctx, c);
+        if (c.kind >= rxp::kConnect && c.o.dev.n_openers != 0) {
+            const fs_status st = connect_host_empty(ctx, c);
+            if (st != FS_SUCCESS) return st;
+        }
+        // no host has a request and no query a reply, yet a flagged query owes its request
+        if (c.kind == rxp::kArp && c.a.dev.n_hosts != 0) return arp_host_empty(ctx, c);
         return FS_SUCCESS;
     }
     RxExtra e(c);  // the own arrays of the accept, the close and the connect call
@@ -515,18 +637,22 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
     const rxp::Layout L = rxp::layout(c.kind, n, s.n_socks);
     e.L = rxp::extra_layout(rxp::kAccept, c.kind, L.bytes, extra_counts(c));
     // the UDP call's own arrays behind them, and the cells' span (the kernels address cells at base + cells_off)
-    const bool udp = c.kind == rxp::kUdp;
+    const bool udp = c.kind >= rxp::kUdp;
     const framesum::RxUdp& hu = c.p.dev;
     const rxp::UdpLayout UL = rxp::udp_layout(e.L.bytes, udp ? n : 0, udp ? hu.n_ports : 0);
     const uint64_t cspan = c.p.span.hi - c.p.span.lo;
     void* const h_udp[rxp::kUdpArrays] = {hu.ports_out, hu.port_of, hu.cell_of};
+    // the ARP call's own arrays behind those
+    const bool arp = c.kind == rxp::kArp;
+    RxArpArrays ea(c.a.dev);
+    ea.L = rxp::arp_layout(UL.bytes, arp ? arp_counts(c.a.dev, n) : rxp::ArpCounts{});
     fs_status st = begin_host_call(ctx);
     if (st == FS_SUCCESS && sockets) st = ctx->dl_rings.grow(ctx, span);
     // (the socket calls begin once more, behind the rings' buffer: a second hipSetDevice that keeps their
     // sequence of HIP calls what profiles/rx_call_refactor/calls.txt compares)
     if (st == FS_SUCCESS && sockets) st = begin_host_call(ctx);
     if (st == FS_SUCCESS) st = ctx->co_payload.grow(ctx, d_cap);
-    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, UL.bytes);
+    if (st == FS_SUCCESS) st = ctx->rx_arrays.grow(ctx, ea.L.bytes);
     if (st == FS_SUCCESS && udp) st = ctx->ud_cells.grow(ctx, cspan);
     if (st != FS_SUCCESS) return st;
     Staged sg;
@@ -550,6 +676,11 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
         // the span goes in first, so that the copy back returns the caller's own bytes around the written cells
         if (cspan != 0)
             FS_HIP_DRAIN(ctx, hipMemcpyAsync(ctx->ud_cells.p, hu.cells + c.p.span.lo, cspan, hipMemcpyHostToDevice, sg.ks));
+    }
+    if (arp) {
+        st = arp_in(ctx, ea, sg.ks);
+        if (st != FS_SUCCESS) return st;
+        d.w = arp_device(c.a.dev, ea);
     }
     RxLeft left;
     st = rx_run(ctx, c, d, left);
@@ -586,6 +717,10 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
             FS_HIP_DRAIN(ctx, back(h_udp[a], ctx->rx_arrays.p + UL.at[a], UL.room[a]));
         FS_HIP_DRAIN(ctx, back(hu.n_ports ? hu.cells + c.p.span.lo : nullptr, ctx->ud_cells.p, cspan));
     }
+    if (arp) {
+        st = arp_back(ctx, ea, sg.ks);
+        if (st != FS_SUCCESS) return st;
+    }
     FS_HIP_DRAIN(ctx, back(h.out, sg.d_out, (uint64_t)n * sizeof(fs_digest)));
     FS_HIP_DRAIN(ctx, back(h.status, sg.d_st, n));
     st = finish_staged(ctx, sg);
@@ -595,7 +730,7 @@ fs_status rx_host(fs_ctx* ctx, const RxCall& c, uint64_t frames_bytes) {
 
 }  // namespace
 
-// ---- The sixteen entry points: fill the record, check, run.
+// ---- The eighteen entry points: fill the record, check, run.
 
 fs_status fs_coalesce_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
                             uint32_t n, uint32_t mtu, uint32_t flags, uint8_t* payload, uint64_t payload_cap,
@@ -925,6 +1060,80 @@ fs_status fs_udp_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t f
     c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
     c.opening(openers, n_openers, reply_flags, openers_out, replies, reply_out, reply_status);
     c.datagrams(ports, n_ports, cells, cells_bytes, ports_out, port_of, cell_of);
+    const fs_status st = rx_check(ctx, c, false);
+    return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
+}
+
+fs_status fs_arp_flows_batch(fs_ctx* ctx, const uint8_t* frames, const uint64_t* offsets, const uint32_t* lengths,
+                               uint32_t n, uint32_t mtu, uint32_t flags, const fs_rx_sock* socks, uint32_t n_socks,
+                               uint8_t* rings, uint64_t rings_bytes, fs_rx_sock_out* socks_out, uint8_t* delivered,
+                               const fs_rx_snd* snd, fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                               uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots, uint32_t synack_flags,
+                               fs_accept_conn* conns, fs_listener_out* listeners_out, uint32_t* accept_of,
+                               uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status, const fs_cl_sock* closers,
+                               uint32_t n_closers, fs_cl_out* closers_out, fs_cl_out* socks_close, uint8_t* ctl_code,
+                               const fs_cn_sock* openers, uint32_t n_openers, uint32_t reply_flags, fs_cn_out* openers_out,
+                               uint8_t* replies, fs_digest* reply_out, uint8_t* reply_status,
+                               const fs_udp_port* ports, uint32_t n_ports, uint8_t* cells, uint64_t cells_bytes,
+                               fs_udp_port_out* ports_out, uint32_t* port_of, uint32_t* cell_of,
+                               const fs_arp_host* hosts, uint32_t n_hosts, const fs_arp_query* queries, uint32_t n_queries,
+                               uint32_t n_reply_slots, uint32_t arp_flags, fs_arp_host_out* hosts_out,
+                               fs_arp_query_out* queries_out, uint8_t* arp_frames, fs_digest* arp_out, uint8_t* arp_status,
+                               uint8_t* arp_code, uint32_t* arp_of,
+                               uint8_t* payload, uint64_t payload_cap, fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order,
+                               uint32_t* run_of, fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status, void* stream) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kArp, "fs_arp_flows_batch", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
+    c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
+    c.opening(openers, n_openers, reply_flags, openers_out, replies, reply_out, reply_status);
+    c.datagrams(ports, n_ports, cells, cells_bytes, ports_out, port_of, cell_of);
+    c.neighbours(hosts, n_hosts, queries, n_queries, n_reply_slots, arp_flags, hosts_out, queries_out, arp_frames, arp_out,
+                 arp_status, arp_code, arp_of);
+    const fs_status st = rx_check(ctx, c, true);
+    return st != FS_SUCCESS ? st : rx_device(ctx, c, stream);
+}
+
+fs_status fs_arp_flows_batch_host(fs_ctx* ctx, const uint8_t* frames, uint64_t frames_bytes, const uint64_t* offsets,
+                                    const uint32_t* lengths, uint32_t n, uint32_t mtu, uint32_t flags,
+                                    const fs_rx_sock* socks, uint32_t n_socks, uint8_t* rings, uint64_t rings_bytes,
+                                    fs_rx_sock_out* socks_out, uint8_t* delivered, const fs_rx_snd* snd,
+                                    fs_rx_snd_out* snd_out, uint8_t* code, const fs_listener* listeners,
+                                    uint32_t n_listeners, const fs_accept_slot* slots, uint32_t n_slots,
+                                    uint32_t synack_flags, fs_accept_conn* conns, fs_listener_out* listeners_out,
+                                    uint32_t* accept_of, uint8_t* synacks, fs_digest* synack_out, uint8_t* synack_status,
+                                    const fs_cl_sock* closers, uint32_t n_closers, fs_cl_out* closers_out,
+                                    fs_cl_out* socks_close, uint8_t* ctl_code, const fs_cn_sock* openers,
+                                    uint32_t n_openers, uint32_t reply_flags, fs_cn_out* openers_out, uint8_t* replies,
+                                    fs_digest* reply_out, uint8_t* reply_status, const fs_udp_port* ports, uint32_t n_ports,
+                                    uint8_t* cells, uint64_t cells_bytes, fs_udp_port_out* ports_out, uint32_t* port_of,
+                                    uint32_t* cell_of, const fs_arp_host* hosts, uint32_t n_hosts,
+                                    const fs_arp_query* queries, uint32_t n_queries, uint32_t n_reply_slots,
+                                    uint32_t arp_flags, fs_arp_host_out* hosts_out, fs_arp_query_out* queries_out,
+                                    uint8_t* arp_frames, fs_digest* arp_out, uint8_t* arp_status, uint8_t* arp_code,
+                                    uint32_t* arp_of, uint8_t* payload, uint64_t payload_cap,
+                                    fs_rx_run* runs, fs_rx_flow* flows, uint32_t* order, uint32_t* run_of,
+                                    fs_rx_flow_totals* totals, fs_digest* out, uint8_t* status) {
+    if (!ctx) return FS_E_INVALID;
+    ctx->err.clear();
+    RxCall c(rxp::kArp, "fs_arp_flows_batch_host", RxBatch{frames, offsets, lengths, n, mtu, flags});
+    c.coalesce(payload, payload_cap, runs, run_of, totals, out, status);
+    c.flows(flows, order);
+    c.sockets(socks, n_socks, rings, rings_bytes, socks_out, delivered);
+    c.send_side(snd, snd_out, code);
+    c.listening(listeners, n_listeners, slots, n_slots, synack_flags, conns, listeners_out, accept_of, synacks, synack_out,
+                synack_status);
+    c.closing(closers, n_closers, closers_out, socks_close, ctl_code);
+    c.opening(openers, n_openers, reply_flags, openers_out, replies, reply_out, reply_status);
+    c.datagrams(ports, n_ports, cells, cells_bytes, ports_out, port_of, cell_of);
+    c.neighbours(hosts, n_hosts, queries, n_queries, n_reply_slots, arp_flags, hosts_out, queries_out, arp_frames, arp_out,
+                 arp_status, arp_code, arp_of);
     const fs_status st = rx_check(ctx, c, false);
     return st != FS_SUCCESS ? st : rx_host(ctx, c, frames_bytes);
 }

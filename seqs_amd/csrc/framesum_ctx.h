@@ -1,7 +1,7 @@
 // Internal to the host side of the C ABI (framesum_api.cpp: context lifecycle, digest and fill calls;
-// framesum_api_tx.cpp: the TX frame build; framesum_api_rx.cpp: the eight RX call kinds -- the plain and
+// framesum_api_tx.cpp: the TX frame build; framesum_api_rx.cpp: the nine RX call kinds -- the plain and
 // the flow-aware coalesce, the delivery into socket rings, the receive call, the accept call, the close call,
-// the connect call and the UDP call): the context, the error
+// the connect call, the UDP call and the ARP call): the context, the error
 // helpers and macros, the grow-only device buffer, the staging blocks and the launch behind one, and the
 // staging helpers of the host-staged calls that stage one batch through slot 0. Defined in
 // framesum_api.cpp.
@@ -127,6 +127,9 @@ struct fs_ctx {
     // the UDP call: the kernels' scratch, and the cells' span of the host form; the ports and their table
     // are staged through seg_stage like the delivery's block.
     DevBuf ud_scratch, ud_cells;
+    // the ARP call: the kernels' scratch; the hosts, the queries and their tables are staged through
+    // seg_stage like the delivery's block, and the frame kernel reads d_seg_tables.
+    DevBuf ar_scratch;
     std::string err;
 };
 

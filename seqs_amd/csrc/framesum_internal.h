@@ -13,6 +13,7 @@
 #include "../../include/framesum_close.h"
 #include "../../include/framesum_connect.h"
 #include "../../include/framesum_udp.h"
+#include "../../include/framesum_arp.h"
 #include "framesum_choice.h"
 #include "framesum_plan.h"
 
@@ -103,10 +104,10 @@ hipError_t launch_send_rings(const uint8_t* d_block, const segment::Block& b, ui
                              int workgroups, hipStream_t stream);
 
 // ---- The RX calls (framesum_coalesce.hip, framesum_flows.hip, framesum_deliver.hip, framesum_recv.hip,
-// framesum_accept.hip, framesum_close.hip, framesum_connect.hip, framesum_udp.hip). A call is a row of stages on one stream --
+// framesum_accept.hip, framesum_close.hip, framesum_connect.hip, framesum_udp.hip, framesum_arp.hip). A call is a row of stages on one stream --
 // the digest launch and the plain or the flow-aware gather, then the delivery, then the receive call's fold,
 // then the accept call's passive open, then the close call's control walks, then the connect call's active
-// open, then the UDP call's delivery into port queues -- each behind the one before it and reading what it left. The launches take the call as a few records.
+// open, then the UDP call's delivery into port queues, then the ARP call's replies and resolutions -- each behind the one before it and reading what it left. The launches take the call as a few records.
 
 // The batch as the launches read it.
 struct RxBatch {
@@ -193,6 +194,16 @@ AcceptScratch accept_scratch(uint32_t n, uint32_t n_listeners, uint32_t n_slots)
 OwnerScratch owner_scratch(uint32_t n, uint32_t n_owners);
 ConnectScratch connect_scratch(uint32_t n, uint32_t n_openers);
 UdpScratch udp_scratch(uint32_t n, uint32_t n_ports);
+// ArpScratch: 256-byte aligned like UdpScratch (arp_scratch asks the sort for its temporary storage's size
+// when a host is listed); 16 bytes per frame, 8 per reply slot and 8 per query beside it.
+struct ArpScratch {
+    uint64_t rank_in, rank_sorted, slot_frame, slot_host, win, n_rep, sort_temp, sort_bytes, bytes;
+};
+ArpScratch arp_scratch(uint32_t n, uint32_t n_hosts, uint32_t n_queries, uint32_t n_reply_slots);
+// The UDP call's rank-by-sort (framesum_udp.hip): 64-bit keys over their low `bits` bits; with a null
+// `temp` it only reports the temporary storage it needs.
+hipError_t rank_sort_keys(void* temp, size_t& temp_bytes, uint64_t* in, uint64_t* out, uint32_t n, uint32_t bits,
+                          hipStream_t stream);
 
 // What the accept call has beside a receive call's batch and results: the counts of its staged lists and
 // where its own results go on the device (the caller's pointers in the device form, the context's device
@@ -237,6 +248,19 @@ struct RxUdp {
     uint32_t* cell_of;
 };
 
+// What the ARP call has beside a UDP call's: the counts of its lists and where its own results go on the
+// device (arp_out, arp_status, arp_code and arp_of are nullable).
+struct RxArp {
+    uint32_t n_hosts, n_queries, n_reply_slots, arp_flags;
+    fs_arp_host_out* hosts_out;
+    fs_arp_query_out* queries_out;
+    uint8_t* arp_frames;
+    fs_digest* arp_out;
+    uint8_t* arp_status;
+    uint8_t* arp_code;
+    uint32_t* arp_of;
+};
+
 // What the stages of one call leave on the device for the stages behind them: each stage's scratch, laid
 // out as its layout says (all zero for a stage that has not run: an empty batch has no flow stage), and
 // where the gather's count of written payload bytes lies.
@@ -256,6 +280,8 @@ struct RxLeft {
     ConnectScratch cns;
     uint8_t* udp_scratch;
     UdpScratch us;
+    uint8_t* arp_scratch;
+    ArpScratch ars;
 };
 
 // The launches that follow a batch's digest launch on the stream (fs_coalesce_batch in
@@ -312,5 +338,12 @@ hipError_t launch_connect(const RxBatch& b, const RxResults& r, const RxConnect&
 // port. With n of 0 only the out records are written.
 hipError_t launch_udp(const RxBatch& b, const RxResults& r, const RxUdp& u, const RxLeft& left, const uint8_t* d_block,
                       const RxLaunch& how);
+
+// The launches that follow a batch's UDP launches (fs_arp_flows_batch in include/framesum_arp.h) and read
+// the verdicts. `d_block`: the device copy of the staged block (framesum_arp.h block_of), null with no host
+// listed: then one launch writes x.arp_code and x.arp_of and nothing else. `tables` and `tx_workgroups`: as
+// launch_accept's, for the frame kernel. With n of 0 only the out records and the flagged requests are written.
+hipError_t launch_arp(const RxBatch& b, const RxResults& r, const RxArp& x, const RxLeft& left, const uint8_t* d_block,
+                      const SegTables* tables, int tx_workgroups, const RxLaunch& how);
 
 }  // namespace framesum

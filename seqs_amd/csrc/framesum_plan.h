@@ -227,7 +227,7 @@ inline void host_chunks(const uint64_t* offsets, const uint32_t* lengths, uint32
 namespace rx {
 
 // A kind has the arrays of the kinds before it and its own.
-enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv, kAccept, kClose, kConnect, kUdp };
+enum Kind : uint32_t { kPlain, kFlows, kDeliver, kRecv, kAccept, kClose, kConnect, kUdp, kArp };
 enum Array : uint32_t { kTotals, kRuns, kFlowRecs, kOrder, kRunOf, kDelivered, kSocksOut, kSndOut, kCode, kArrays };
 // What counts an array's entries: one record, the batch's frames, the call's sockets, or (for what
 // comes back only) one of the totals.
@@ -379,6 +379,46 @@ inline UdpLayout udp_layout(uint64_t base, uint64_t n, uint64_t n_ports) {
         at = (at + d.align - 1) / d.align * d.align;
         L.at[a] = at;
         L.room[a] = d.elem * (d.count == kPerPort ? n_ports : n);
+        at += L.room[a];
+    }
+    L.bytes = at;
+    return L;
+}
+
+// The own arrays of the ninth kind (fs_arp_flows_batch_host), described the same way: they lie behind
+// udp_layout's rows in the same buffer, in this order. Of the frames, their digests and their verdicts the
+// call writes only the slots that take a frame, so the caller's bytes go to the device first; every array
+// comes back whole. A frame slot is a reply slot or a query's request slot.
+enum ArpArray : uint32_t { kHostsOut, kQueriesOut, kArpFrames, kArpOut, kArpStatus, kArpCode, kArpOf, kArpArrays };
+enum ArpCount : uint32_t { kPerHost, kPerQuery, kPerFrameSlot, kPerArpFrame, kArpCounts };
+struct ArpArrayDesc {
+    uint32_t elem, align;  // bytes per entry, and the alignment the kernels' stores want
+    ArpCount count;
+    bool goes_in;
+};
+constexpr ArpArrayDesc kArpArrayDesc[kArpArrays] = {
+    {16, 4, kPerHost, false},       // fs_arp_host_out
+    {16, 4, kPerQuery, false},      // fs_arp_query_out
+    {64, 1, kPerFrameSlot, true},   // arp_frames (FS_ACCEPT_STRIDE)
+    {8, 8, kPerFrameSlot, true},    // arp_out
+    {1, 1, kPerFrameSlot, true},    // arp_status
+    {1, 1, kPerArpFrame, false},    // arp_code
+    {4, 4, kPerArpFrame, false},    // arp_of
+};
+struct ArpCounts {
+    uint64_t of[kArpCounts];  // by ArpCount
+};
+struct ArpLayout {
+    uint64_t at[kArpArrays], room[kArpArrays], bytes;  // `bytes`: `base` and the rows laid out
+};
+inline ArpLayout arp_layout(uint64_t base, const ArpCounts& counts) {
+    ArpLayout L;
+    uint64_t at = base;
+    for (uint32_t a = 0; a < kArpArrays; ++a) {
+        const ArpArrayDesc& d = kArpArrayDesc[a];
+        at = (at + d.align - 1) / d.align * d.align;
+        L.at[a] = at;
+        L.room[a] = d.elem * counts.of[d.count];
         at += L.room[a];
     }
     L.bytes = at;

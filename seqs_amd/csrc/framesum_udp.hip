@@ -220,18 +220,19 @@ __global__ void __launch_bounds__(kThreads) udp_copy_narrow(const UdArgs a) {
     }
 }
 
-hipError_t sort_keys(void* temp, size_t& temp_bytes, uint64_t* in, uint64_t* out, uint32_t n, uint32_t bits,
-                     hipStream_t stream) {
+}  // namespace
+
+// The rank-by-sort of this call, which the ARP call's launches (framesum_arp.hip) use as it is.
+hipError_t rank_sort_keys(void* temp, size_t& temp_bytes, uint64_t* in, uint64_t* out, uint32_t n, uint32_t bits,
+                          hipStream_t stream) {
     return rocprim::radix_sort_keys(temp, temp_bytes, in, out, n, 0u, bits, stream);
 }
-
-}  // namespace
 
 UdpScratch udp_scratch(uint32_t n, uint32_t n_ports) {
     UdpScratch s;
     size_t sort_bytes = 0;
     // (a null pointer: the sort only reports what it needs)
-    if (n != 0 && sort_keys(nullptr, sort_bytes, nullptr, nullptr, n, udp::rank_bits(flows::index_bits(n), n_ports), nullptr) !=
+    if (n != 0 && rank_sort_keys(nullptr, sort_bytes, nullptr, nullptr, n, udp::rank_bits(flows::index_bits(n), n_ports), nullptr) !=
                       hipSuccess)
         sort_bytes = 0;
     uint64_t at = 0;
@@ -284,7 +285,7 @@ hipError_t launch_udp(const RxBatch& b, const RxResults& r, const RxUdp& u, cons
     if (n == 0) return hipGetLastError();
     hipLaunchKernelGGL(udp_mark, dim3(g.scan), dim3(kThreads), 0, stream, a);
     size_t sort_bytes = s.sort_bytes;
-    const hipError_t e = sort_keys(scratch + s.sort_temp, sort_bytes, a.rank_in, reinterpret_cast<uint64_t*>(scratch + s.rank_sorted),
+    const hipError_t e = rank_sort_keys(scratch + s.sort_temp, sort_bytes, a.rank_in, reinterpret_cast<uint64_t*>(scratch + s.rank_sorted),
                                    n, udp::rank_bits(a.b, u.n_ports), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(udp_assign, dim3(g.scan), dim3(kThreads), 0, stream, a);

@@ -35,6 +35,9 @@ from .abi import (  # noqa: F401 (re-exported: this module is the binding's publ
     SEND_RINGS_PROTOTYPES, SND_DTYPE, SND_OUT_DTYPE, SOCK_DTYPE, SOCK_OUT_DTYPE, TEST_LIB_PATH, TOTALS_DTYPE, TX_ACK, TX_FIN,
     TX_PSH, TX_SOCK_DTYPE, TX_SOCK_OUT_DTYPE, VERDICTS, FramesumError, lib_path, load_library, sock_key,
     UDP_CELL_DTYPE, UDP_CELL_HEADER, UDP_FULL, UDP_MAX_PORTS, UDP_NONE, UDP_PORT_DTYPE, UDP_PORT_OUT_DTYPE, UDP_PROTOTYPES,
+    ARP_ANSWERED, ARP_FRAME, ARP_FRAME_PADDED, ARP_FULL, ARP_HOST_DTYPE, ARP_HOST_OUT_DTYPE, ARP_IGNORED, ARP_MAX_HOSTS,
+    ARP_MAX_QUERIES, ARP_MAX_REPLY_SLOTS, ARP_NONE, ARP_NOT_ARP, ARP_PAD, ARP_PROTOTYPES, ARP_Q_DONE, ARP_Q_SENT, ARP_Q_WAIT,
+    ARP_QUERY_DTYPE, ARP_QUERY_OUT_DTYPE, ARP_RESOLVED, ARP_SEND_REQUEST, ARP_STALE, ARP_UNSUPPORTED,
 )
 
 _vp, _u64 = ctypes.c_void_p, ctypes.c_uint64
@@ -95,6 +98,7 @@ _RX_ACCEPT = ("fs_accept_flows_batch", *_RX_FLOWS[1:])  # (the receive call with
 _RX_CLOSE = ("fs_close_flows_batch", *_RX_FLOWS[1:])  # (the accept call with the closing arguments behind synack_status)
 _RX_CONNECT = ("fs_connect_flows_batch", *_RX_FLOWS[1:])  # (the close call with the opening arguments behind ctl_code)
 _RX_UDP = ("fs_udp_flows_batch", *_RX_FLOWS[1:])  # (the connect call with the port arguments behind reply_status)
+_RX_ARP = ("fs_arp_flows_batch", *_RX_FLOWS[1:])  # (the UDP call with the host and query arguments behind cell_of)
 
 
 @dataclass
@@ -652,6 +656,28 @@ class Engine(_Handle):
                     args += (_array_ptr(ports), int(ports.size), ptr(cells), cells.numel(), ptr(ports_out), ptr(port_of),
                              ptr(cell_of))
                     rx, mine = _RX_UDP, (ports_out, port_of, cell_of, *mine)
+                    if len(_closing) > 4:  # arp_flows_device: the host and query arguments behind cell_of, its tensors in front
+                        hosts, queries, n_reply, arp_flags, arp_frames, arp_results, want_code, want_of = _closing[4]
+                        n_frames = n_reply + int(queries.size)
+                        if arp_frames is None:
+                            arp_frames = torch.zeros((n_frames * ACCEPT_STRIDE,), dtype=torch.uint8, device=dev)
+                        assert arp_frames.is_cuda and arp_frames.dtype == torch.uint8 and arp_frames.is_contiguous()
+                        assert arp_frames.numel() >= n_frames * ACCEPT_STRIDE, "arp_frames holds ACCEPT_STRIDE bytes per slot"
+                        hosts_out = torch.empty((int(hosts.size), ARP_HOST_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                        queries_out = torch.empty((int(queries.size), ARP_QUERY_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                        if isinstance(arp_results, tuple):  # the caller's own (slots, 2) int32 and (slots,) uint8 tensors
+                            arp_out, arp_st = arp_results
+                            assert arp_out.is_cuda and arp_out.dtype == torch.int32 and arp_out.numel() == 2 * n_frames
+                            assert arp_st.is_cuda and arp_st.dtype == torch.uint8 and arp_st.numel() == n_frames
+                        else:
+                            arp_out = torch.zeros((n_frames, 2), dtype=torch.int32, device=dev) if arp_results else None
+                            arp_st = torch.zeros((n_frames,), dtype=torch.uint8, device=dev) if arp_results else None
+                        arp_code = torch.empty((n,), dtype=torch.uint8, device=dev) if want_code else None
+                        arp_of = torch.empty((n,), dtype=torch.int32, device=dev) if want_of else None
+                        args += (_array_ptr(hosts), int(hosts.size), _array_ptr(queries), int(queries.size), n_reply, arp_flags,
+                                 ptr(hosts_out), ptr(queries_out), ptr(arp_frames), ptr(arp_out), ptr(arp_st), ptr(arp_code),
+                                 ptr(arp_of))
+                        rx, mine = _RX_ARP, (hosts_out, queries_out, arp_frames, arp_out, arp_st, arp_code, arp_of, *mine)
         return (*mine, conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
                 *self._rx_device(rx, frames, offsets, lengths, mtu, flags, payload, stream, args))
 
@@ -730,6 +756,29 @@ class Engine(_Handle):
                     args += (_array_ptr(ports), int(ports.size), ptr(cells), cells.nbytes, ptr(ports_out), ptr(port_of),
                              ptr(cell_of))
                     rx, mine = _RX_UDP, (ports_out, port_of, cell_of, *mine)
+                    if len(_closing) > 4:  # arp_flows_host
+                        hosts, queries, n_reply, arp_flags, arp_frames, arp_results, want_code, want_of = _closing[4]
+                        n_frames = n_reply + int(queries.size)
+                        if arp_frames is None:
+                            arp_frames = np.zeros(n_frames * ACCEPT_STRIDE, dtype=np.uint8)
+                        assert isinstance(arp_frames, np.ndarray) and arp_frames.dtype == np.uint8
+                        assert arp_frames.flags["C_CONTIGUOUS"] and arp_frames.flags["WRITEABLE"]
+                        assert arp_frames.size >= n_frames * ACCEPT_STRIDE, "arp_frames holds ACCEPT_STRIDE bytes per slot"
+                        hosts_out = np.zeros(int(hosts.size), dtype=ARP_HOST_OUT_DTYPE)
+                        queries_out = np.zeros(int(queries.size), dtype=ARP_QUERY_OUT_DTYPE)
+                        if isinstance(arp_results, tuple):  # the caller's own DIGEST_DTYPE[slots] and uint8[slots] arrays
+                            arp_out, arp_st = arp_results
+                            assert arp_out.dtype == DIGEST_DTYPE and arp_out.size == n_frames and arp_out.flags["C_CONTIGUOUS"]
+                            assert arp_st.dtype == np.uint8 and arp_st.size == n_frames and arp_st.flags["C_CONTIGUOUS"]
+                        else:
+                            arp_out = np.zeros(n_frames, dtype=DIGEST_DTYPE) if arp_results else None
+                            arp_st = np.zeros(n_frames, dtype=np.uint8) if arp_results else None
+                        arp_code = np.zeros(n, dtype=np.uint8) if want_code else None
+                        arp_of = np.full(n, ARP_NONE, dtype=np.uint32) if want_of else None
+                        args += (_array_ptr(hosts), int(hosts.size), _array_ptr(queries), int(queries.size), n_reply, arp_flags,
+                                 ptr(hosts_out), ptr(queries_out), ptr(arp_frames), ptr(arp_out), ptr(arp_st), ptr(arp_code),
+                                 ptr(arp_of))
+                        rx, mine = _RX_ARP, (hosts_out, queries_out, arp_frames, arp_out, arp_st, arp_code, arp_of, *mine)
         return (*mine, conns, listeners_out, of, synacks, syn_out, syn_st, snd_out, codes, socks_out, marks,
                 *self._rx_host(rx, frames, offsets, lengths, mtu, flags, payload, args))
 
@@ -829,6 +878,65 @@ class Engine(_Handle):
         return self.accept_flows_host(frames, offsets, lengths, socks, snd, rings, listeners, slots,
                                       _closing=(closers, ctl_code, (openers, reply_flags, replies, reply_results),
                                                 (ports, cells, port_of, cell_of)), **kw)
+
+    # ---- the ARP call: the UDP call plus the ARP branch of RecvEth (include/framesum_arp.h) ----
+    def arp_flows_device(self, frames, offsets, lengths, socks: np.ndarray, snd: np.ndarray, rings,
+                         listeners: np.ndarray, slots: np.ndarray, closers: np.ndarray, openers: np.ndarray,
+                         ports: np.ndarray, cells, hosts: np.ndarray, queries: np.ndarray, n_reply_slots: int = None,
+                         arp_flags: int = 0, arp_frames=None, arp_results=True, arp_code: bool = True, arp_of: bool = True,
+                         port_of: bool = True, cell_of: bool = True, reply_flags: int = 0, replies=None,
+                         reply_results: bool = True, ctl_code: bool = True, **kw):
+        """udp_flows_device plus the ARP branch of RecvEth (fs_arp_flows_batch): `hosts` is an ARP_HOST_DTYPE
+        array on the host (arp_host() makes one row: a local interface, its range of reply slots), `queries`
+        an ARP_QUERY_DTYPE array on the host (arp_query(): a resolution in progress, or with ARP_SEND_REQUEST
+        one whose who-has frame is to be built). Every ARP request for a host's address is answered in the
+        host's next free slot, in batch order; every ARP reply resolves the query it matches. `n_reply_slots`:
+        the reply slots in `arp_frames` (the end of the hosts' ranges unless given); query q's request goes to
+        slot n_reply_slots + q. `arp_frames`: a uint8 CUDA tensor of ACCEPT_STRIDE bytes per slot (else a new
+        zeroed one), of which only the built frames' bytes are written. Further keyword arguments are
+        accept_flows_device's. Returns (hosts_out, queries_out, arp_frames, arp_out, arp_status, arp_code, arp_of,
+        then udp_flows_device's tuple) device tensors: hosts_out (n_hosts, 16) and queries_out (n_queries, 16)
+        uint8 = ARP_HOST_OUT_DTYPE / ARP_QUERY_OUT_DTYPE records, arp_out (slots, 2) int32 and arp_status
+        (slots,) uint8 as digest_device gives them, written for built frames only (zeroed here first; None when
+        `arp_results` is False; the caller's own pair when it is a tuple), arp_code (n,) uint8 and arp_of (n,)
+        int32 (-1 = ARP_NONE; None when the flag is False). Asynchronous on `stream`; split_arp() brings
+        the results to the host."""
+        closers = np.ascontiguousarray(closers, dtype=CLOSER_DTYPE)
+        openers = np.ascontiguousarray(openers, dtype=OPENER_DTYPE)
+        ports = np.ascontiguousarray(ports, dtype=UDP_PORT_DTYPE)
+        hosts = np.ascontiguousarray(hosts, dtype=ARP_HOST_DTYPE)
+        queries = np.ascontiguousarray(queries, dtype=ARP_QUERY_DTYPE)
+        if n_reply_slots is None:
+            n_reply_slots = arp_reply_slots(hosts)
+        return self.accept_flows_device(frames, offsets, lengths, socks, snd, rings, listeners, slots,
+                                        _closing=(closers, ctl_code, (openers, reply_flags, replies, reply_results),
+                                                  (ports, cells, port_of, cell_of),
+                                                  (hosts, queries, int(n_reply_slots), arp_flags, arp_frames, arp_results,
+                                                   arp_code, arp_of)), **kw)
+
+    def arp_flows_host(self, frames: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, socks: np.ndarray,
+                       snd: np.ndarray, rings: np.ndarray, listeners: np.ndarray, slots: np.ndarray, closers: np.ndarray,
+                       openers: np.ndarray, ports: np.ndarray, cells: np.ndarray, hosts: np.ndarray, queries: np.ndarray,
+                       n_reply_slots: int = None, arp_flags: int = 0, arp_frames=None, arp_results=True,
+                       arp_code: bool = True, arp_of: bool = True, port_of: bool = True, cell_of: bool = True,
+                       reply_flags: int = 0, replies=None, reply_results: bool = True, ctl_code: bool = True, **kw):
+        """arp_flows_device from and to host memory (fs_arp_flows_batch_host). `arp_frames`: a writable uint8
+        array of ACCEPT_STRIDE bytes per slot (else a new zeroed one), written in place in the built frames'
+        bytes only. Returns (hosts_out ARP_HOST_OUT_DTYPE[n_hosts], queries_out ARP_QUERY_OUT_DTYPE[n_queries],
+        arp_frames, arp_out DIGEST_DTYPE[slots] or None, arp_status uint8[slots] or None, arp_code uint8[n] or
+        None, arp_of uint32[n] or None, then udp_flows_host's tuple)."""
+        closers = np.ascontiguousarray(closers, dtype=CLOSER_DTYPE)
+        openers = np.ascontiguousarray(openers, dtype=OPENER_DTYPE)
+        ports = np.ascontiguousarray(ports, dtype=UDP_PORT_DTYPE)
+        hosts = np.ascontiguousarray(hosts, dtype=ARP_HOST_DTYPE)
+        queries = np.ascontiguousarray(queries, dtype=ARP_QUERY_DTYPE)
+        if n_reply_slots is None:
+            n_reply_slots = arp_reply_slots(hosts)
+        return self.accept_flows_host(frames, offsets, lengths, socks, snd, rings, listeners, slots,
+                                      _closing=(closers, ctl_code, (openers, reply_flags, replies, reply_results),
+                                                (ports, cells, port_of, cell_of),
+                                                (hosts, queries, int(n_reply_slots), arp_flags, arp_frames, arp_results,
+                                                 arp_code, arp_of)), **kw)
 
     # ---- TCP segments from socket TX rings (include/framesum_send.h) ------------
     @staticmethod
@@ -1147,6 +1255,83 @@ def ports_after(ports, ports_out, consumed=None):
                                              else outs["n_admitted"].astype(np.uint64))
     assert (free <= nxt["n_cells"]).all(), "more cells handed back than the queue has in use"
     nxt["free"] = free
+    return nxt
+
+
+def _ip4(ip) -> np.ndarray:
+    """An IPv4 address (4 bytes, a dotted string or an integer) as its 4 wire bytes."""
+    return sock_key(0, 0, ip, 1)[5:9].copy()
+
+
+def _mac6(mac) -> np.ndarray:
+    """A MAC address (6 bytes, or a colon-separated string) as its 6 wire bytes."""
+    if isinstance(mac, str):
+        mac = bytes(int(x, 16) for x in mac.split(":"))
+    m = np.frombuffer(bytes(mac), dtype=np.uint8)
+    assert m.size == 6, "a MAC address has 6 bytes"
+    return m
+
+
+def arp_host(ip, mac, slot0: int = 0, free: int = 1):
+    """One ARP_HOST_DTYPE row: a local interface with address `ip` (4 bytes, a dotted string or an integer) and
+    `mac` (6 bytes or aa:bb:cc:dd:ee:ff), which may emit `free` replies in a call, into the reply slots from
+    `slot0` on."""
+    row = np.zeros(1, dtype=ARP_HOST_DTYPE)
+    row["ip"][0], row["mac"][0] = _ip4(ip), _mac6(mac)
+    row["slot0"], row["free"] = slot0, free
+    return row
+
+
+def arp_query(host: int, target, send: bool = False):
+    """One ARP_QUERY_DTYPE row: host number `host` resolves `target`. With `send` the call builds the who-has
+    frame (and the query takes no reply in that call); without, the query waits for its reply."""
+    row = np.zeros(1, dtype=ARP_QUERY_DTYPE)
+    row["host"], row["target"][0], row["flags"] = host, _ip4(target), ARP_SEND_REQUEST if send else 0
+    return row
+
+
+def arp_reply_slots(hosts) -> int:
+    """The reply slots a host list needs: the end of its last range."""
+    hosts = np.atleast_1d(np.asarray(hosts, dtype=ARP_HOST_DTYPE))
+    return int((hosts["slot0"].astype(np.uint64) + hosts["free"]).max()) if hosts.size else 0
+
+
+def split_arp(hosts, queries, hosts_out, queries_out, arp_frames, n_reply_slots=None, arp_flags: int = 0):
+    """What an ARP call produced, as Python values: (replies, requests, resolutions). `replies`: per host the
+    list of its built reply frames (bytes, the FCS included when arp_flags has FCS_APPEND) in the order of the
+    requests they answer; `requests`: {query number: who-has frame} of the queries flagged ARP_SEND_REQUEST;
+    `resolutions`: {query number: (mac bytes, batch index of the reply)} of the queries that came back done.
+    Tensors are waited for and brought to the host."""
+    hosts = np.atleast_1d(np.asarray(hosts, dtype=ARP_HOST_DTYPE))
+    queries = np.atleast_1d(np.asarray(queries, dtype=ARP_QUERY_DTYPE))
+    h_out = np.atleast_1d(_records(hosts_out, ARP_HOST_OUT_DTYPE))
+    q_out = np.atleast_1d(_records(queries_out, ARP_QUERY_OUT_DTYPE))
+    assert hosts.size == h_out.size and queries.size == q_out.size, "one out record per host and per query"
+    buf = _records(arp_frames, np.uint8).reshape(-1)
+    if n_reply_slots is None:
+        n_reply_slots = arp_reply_slots(hosts)
+    size = (ARP_FRAME_PADDED if arp_flags & ARP_PAD else ARP_FRAME) + (4 if arp_flags & FCS_APPEND else 0)
+
+    def frame(slot):
+        return bytes(buf[slot * ACCEPT_STRIDE : slot * ACCEPT_STRIDE + size])
+
+    replies = [[frame(int(h["slot0"]) + r) for r in range(int(o["n_answered"]))] for h, o in zip(hosts, h_out)]
+    requests = {q: frame(n_reply_slots + q) for q in range(queries.size) if int(q_out[q]["state"]) == ARP_Q_SENT}
+    resolutions = {q: (bytes(q_out[q]["mac"]), int(q_out[q]["frame"])) for q in range(queries.size)
+                   if int(q_out[q]["state"]) == ARP_Q_DONE}
+    return replies, requests, resolutions
+
+
+def hosts_after(hosts, hosts_out=None, free=None):
+    """The host list for the next call: `hosts` with `free` replies each again (one number for all, or an
+    array; what each host had before the call unless given -- the caller has sent the built replies)."""
+    nxt = np.atleast_1d(np.asarray(hosts, dtype=ARP_HOST_DTYPE)).copy()
+    if hosts_out is not None:
+        outs = np.atleast_1d(_records(hosts_out, ARP_HOST_OUT_DTYPE))
+        assert nxt.size == outs.size, "one out record per host"
+        assert (outs["free"].astype(np.uint64) + outs["n_answered"] == nxt["free"]).all(), "hosts_out is not these hosts'"
+    if free is not None:
+        nxt["free"] = free
     return nxt
 
 
