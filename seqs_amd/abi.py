@@ -148,6 +148,15 @@ TX_SOCK_OUT_DTYPE = np.dtype([("snd_nxt", "<u4"), ("ring_rpos", "<u4"), ("ring_b
 SEND_MAX_SOCKS = 65536
 SEND_NONE = 0xFFFFFFFF  # fs_tx_sock_out.first_frame of a socket that made no frame
 TX_ACK, TX_FIN, TX_PSH = 1, 2, 4  # fs_tx_sock.flags
+# The resident ring send (include/framesum_send_resident.h): fs_tx_totals (40 bytes, no padding), the call
+# flag, the two per-socket outcomes in fs_tx_sock_out.sent and the reasons of an invalid socket (bits 16..)
+TX_TOTALS_DTYPE = np.dtype([("n_frames", "<u8"), ("frames_bytes", "<u8"), ("data_bytes", "<u8"), ("n_built", "<u4"),
+                            ("n_idle", "<u4"), ("n_deferred", "<u4"), ("n_invalid", "<u4")])
+TX_WRITEBACK = 0x100
+TX_DEFERRED, TX_INVALID = 0x100, 0x200
+TX_NO_RX = 0xFFFFFFFF  # an rx_index entry: the socket has no RX record
+(TX_BAD_ETHERTYPE, TX_BAD_IHL, TX_BAD_PROTO, TX_BAD_DATA_OFFSET, TX_BAD_MSS, TX_BAD_SOCK_FLAGS, TX_BAD_MAX_FRAMES,
+ TX_BAD_RING_SIZE, TX_BAD_RING_POS, TX_BAD_BUFFERED, TX_BAD_RING_RANGE, TX_BAD_RX_INDEX) = range(1, 13)
 
 
 def sock_key(remote_ip, remote_port: int, local_ip, local_port: int) -> np.ndarray:
@@ -308,6 +317,12 @@ ARP_PROTOTYPES = {
                                 + UDP_PROTOTYPES["fs_udp_flows_batch_host"][1][47:]),
 }
 
+# The function include/framesum_send_resident.h declares (the tenth header): a product symbol too.
+SEND_RESIDENT_PROTOTYPES = {
+    "fs_send_rings_resident": (_st, [_p, _p, _u32, _p, _p, _p, _u32, _p, _u64, _u32, _u32, _u32, _p, _u64, _u32,
+                                     _p, _p, _p, _p, _p, _p, _p]),
+}
+
 # Not in the header, set only where the loaded library has them: the test library's hooks
 # (-DFS_TEST_HOOKS) and the diagnostic build's stamp reader (tools/stamps.py).
 OPTIONAL_PROTOTYPES = {
@@ -345,7 +360,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib = ctypes.CDLL(p)
     tables = {**PROTOTYPES, **DELIVER_PROTOTYPES, **SEND_RINGS_PROTOTYPES, **RECV_PROTOTYPES, **ACCEPT_PROTOTYPES,
               **CLOSE_PROTOTYPES, **CONNECT_PROTOTYPES, **UDP_PROTOTYPES, **ARP_PROTOTYPES,
-              **OPTIONAL_PROTOTYPES}
+              **SEND_RESIDENT_PROTOTYPES, **OPTIONAL_PROTOTYPES}
     for name, (restype, argtypes) in tables.items():
         if (name in OPTIONAL_PROTOTYPES or name in _MAY_BE_ABSENT) and not hasattr(lib, name):
             continue

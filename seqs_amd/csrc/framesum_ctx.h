@@ -130,6 +130,9 @@ struct fs_ctx {
     // the ARP call: the kernels' scratch; the hosts, the queries and their tables are staged through
     // seg_stage like the delivery's block, and the frame kernel reads d_seg_tables.
     DevBuf ar_scratch;
+    // the resident ring send: the plan kernels' sums, the head and the block they stage for the frame kernel
+    // (framesum_send_resident.h scratch_of)
+    DevBuf sr_scratch;
     std::string err;
 };
 

@@ -103,6 +103,19 @@ hipError_t launch_send_rings(const uint8_t* d_block, const segment::Block& b, ui
                              uint8_t* status, uint32_t mtu, uint32_t flags, uint32_t align, const SegTables* tables,
                              int workgroups, hipStream_t stream);
 
+// ---- Resident ring send (framesum_send_resident.hip; its arithmetic: framesum_send_resident.h). The four
+// launches of fs_send_rings_resident: the three plan kernels over `c`'s device socket table, which leave the
+// head and send::stage's block in `scratch` (laid out as `sl`), and the frame kernel behind them, whose grid
+// is sized from c.frames_cap. `plan_workgroups` and `tx_workgroups` cap the grids.
+namespace resident {
+struct Call;
+struct Scratch;
+}  // namespace resident
+hipError_t launch_send_resident(resident::Call c, uint8_t* scratch, const resident::Scratch& sl, const uint8_t* rings,
+                                uint8_t* frames, uint64_t* offsets, uint32_t* lengths, void* out, uint8_t* status,
+                                uint32_t mtu, const SegTables* tables, int plan_workgroups, int tx_workgroups,
+                                hipStream_t stream);
+
 // ---- The RX calls (framesum_coalesce.hip, framesum_flows.hip, framesum_deliver.hip, framesum_recv.hip,
 // framesum_accept.hip, framesum_close.hip, framesum_connect.hip, framesum_udp.hip, framesum_arp.hip). A call is a row of stages on one stream --
 // the digest launch and the plain or the flow-aware gather, then the delivery, then the receive call's fold,

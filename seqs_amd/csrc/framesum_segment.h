@@ -12,6 +12,14 @@
 
 #include "../../include/framesum.h"
 
+// The arithmetic the device plan of the resident ring send (framesum_send_resident.hip) runs too is
+// marked FS_HD: callable from device code in a HIP translation unit, plain inline functions elsewhere.
+#if defined(__HIP__)
+#define FS_HD __host__ __device__
+#else
+#define FS_HD
+#endif
+
 namespace framesum {
 namespace segment {
 
@@ -34,8 +42,8 @@ static_assert(prand16(1) == 0x8181, "prand16");
 // kIdStride steps at once: prand16 is linear over GF(2) (XORs of shifts), so its 64th power is the
 // XOR of the images of x's bits.
 struct Prand16Stride {
-    uint16_t image[16];
-    Prand16Stride() {
+    uint16_t image[16] = {};
+    constexpr Prand16Stride() {
         for (int b = 0; b < 16; ++b) {
             uint16_t v = (uint16_t)(1u << b);
             for (uint32_t i = 0; i < kIdStride; ++i) v = prand16(v);
@@ -43,8 +51,8 @@ struct Prand16Stride {
         }
     }
 };
-inline uint16_t prand16_stride(uint16_t x) {
-    static const Prand16Stride t;
+FS_HD inline uint16_t prand16_stride(uint16_t x) {
+    constexpr Prand16Stride t;  // (16 constants: the same on the host and in a kernel)
     uint16_t r = 0;
     for (int b = 0; b < 16; ++b)
         if ((x >> b) & 1u) r = (uint16_t)(r ^ t.image[b]);
@@ -66,7 +74,7 @@ inline uint32_t frames_of(const fs_tx_send& s) {
     return (uint32_t)(((uint64_t)s.payload_len + s.mss - 1) / s.mss);
 }
 // bytes [k mss, (k + 1) mss) of `total` (none behind its end); mss == 0: all of them
-inline uint32_t chunk_at(uint32_t total, uint32_t mss, uint32_t k) {
+FS_HD inline uint32_t chunk_at(uint32_t total, uint32_t mss, uint32_t k) {
     if (mss == 0) return total;
     const uint64_t lo = (uint64_t)k * mss;
     return lo >= total ? 0u : (uint32_t)(total - lo < mss ? total - lo : mss);
@@ -182,7 +190,7 @@ struct Block {
     uint64_t recs_at = 0, prefix_at = 0, ids_at = 0, bytes = 0;
 };
 // n_recs records of rec_bytes each: the layout of this call's block and of the ring send's
-inline Block block_of(uint32_t n_recs, uint64_t rec_bytes, uint64_t id_entries) {
+FS_HD inline Block block_of(uint32_t n_recs, uint64_t rec_bytes, uint64_t id_entries) {
     Block b;
     b.recs_at = 0;
     b.prefix_at = (uint64_t)n_recs * rec_bytes;
@@ -193,7 +201,7 @@ inline Block block_of(uint32_t n_recs, uint64_t rec_bytes, uint64_t id_entries) 
 inline Block block_of(uint32_t n_sends, uint64_t id_entries) { return block_of(n_sends, sizeof(SendRec), id_entries); }
 // A record's staged ID powers, ceil(frames / kIdStride) of them from ids[id_at] on: the IDs of its
 // frames 0, kIdStride, 2 kIdStride, ... Returns the index behind them.
-inline uint64_t stage_ids(uint16_t id, uint32_t frames, uint16_t* ids, uint64_t id_at) {
+FS_HD inline uint64_t stage_ids(uint16_t id, uint32_t frames, uint16_t* ids, uint64_t id_at) {
     for (uint32_t k = 0; k < frames; k += kIdStride) {
         ids[id_at++] = id;
         id = prand16_stride(id);
@@ -259,7 +267,7 @@ inline uint32_t find_send(const uint32_t* prefix, uint32_t n_sends, uint32_t fra
 
 // Frames a wave builds back to back before it looks its next frame's send up again: enough that
 // the lookups are few, few enough that a small batch still spreads over the waves.
-inline uint32_t tile_frames(uint64_t n_frames, uint32_t waves) {
+FS_HD inline uint32_t tile_frames(uint64_t n_frames, uint32_t waves) {
     const uint64_t t = (n_frames + waves - 1) / (waves ? waves : 1);
     return t < 1 ? 1u : t > 16 ? 16u : (uint32_t)t;
 }

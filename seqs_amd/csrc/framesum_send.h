@@ -4,7 +4,9 @@
 // the layout, and the block of per-socket records a call stages for the kernel (framesum_send.hip
 // reads exactly these structs). The slots, the chunks, the block's layout, the ID powers and the
 // frame -> record search are the TX frame build's (framesum_segment.h). tests/csrc/test_send.cpp builds
-// it alone under ASan + UBSan.
+// it alone under ASan + UBSan. The checks, the rule and the records are marked FS_HD: the plan kernels of
+// the resident ring send (framesum_send_resident.h, framesum_send_resident.hip) run them per socket on
+// the device, so the rule stays written once.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -61,7 +63,7 @@ inline const char* bad_text(Bad b) {
 }
 
 // One socket's checks. `have_rings` false: fs_send_rings_layout has no rings_bytes to bound the ring with.
-inline Bad check_sock(const fs_tx_sock& s, bool have_rings, uint64_t rings_bytes) {
+FS_HD inline Bad check_sock(const fs_tx_sock& s, bool have_rings, uint64_t rings_bytes) {
     if (s.hdr[12] != 0x08 || s.hdr[13] != 0x00) return kBadEtherType;
     if ((s.hdr[14] & 0x0F) != 5) return kBadIhl;
     if (s.hdr[23] != 6) return kBadProto;
@@ -84,11 +86,11 @@ struct Plan {
     bool fin = false;
     uint8_t tcp_flags = 0;  // of the socket's LAST frame (the kernel clears FIN and PSH on the others)
 };
-inline uint32_t room_of(const fs_tx_sock& s) {
+FS_HD inline uint32_t room_of(const fs_tx_sock& s) {
     const uint32_t in_flight = s.snd_nxt - s.snd_una;
     return s.snd_wnd > in_flight ? s.snd_wnd - in_flight : 0u;  // (the reference panics when in_flight > snd_wnd)
 }
-inline Plan plan_of(const fs_tx_sock& s) {
+FS_HD inline Plan plan_of(const fs_tx_sock& s) {
     Plan p;
     const uint32_t cap = (s.max_frames ? s.max_frames : FS_SEGMENT_MAX_FRAMES) * (uint32_t)s.mss;  // <= 4096 * 65495
     const uint32_t room = room_of(s);
@@ -101,15 +103,15 @@ inline Plan plan_of(const fs_tx_sock& s) {
     p.tcp_flags = (uint8_t)(kTcpAck | ((s.flags & FS_TX_PSH) && p.data ? kTcpPsh : 0) | (p.fin ? kTcpFin : 0));
     return p;
 }
-inline uint32_t chunk_of(const fs_tx_sock& s, const Plan& p, uint32_t k) { return segment::chunk_at(p.data, s.mss, k); }
+FS_HD inline uint32_t chunk_of(const fs_tx_sock& s, const Plan& p, uint32_t k) { return segment::chunk_at(p.data, s.mss, k); }
 // prand16 applied n times (n <= FS_SEGMENT_MAX_FRAMES): kIdStride steps at once, then the rest
-inline uint16_t advance_id(uint16_t id, uint32_t n) {
+FS_HD inline uint16_t advance_id(uint16_t id, uint32_t n) {
     for (; n >= segment::kIdStride; n -= segment::kIdStride) id = segment::prand16_stride(id);
     for (; n > 0; --n) id = segment::prand16(id);
     return id;
 }
-inline uint16_t template_id(const fs_tx_sock& s) { return (uint16_t)((s.hdr[18] << 8) | s.hdr[19]); }
-inline fs_tx_sock_out out_of(const fs_tx_sock& s, const Plan& p, uint64_t first_frame) {
+FS_HD inline uint16_t template_id(const fs_tx_sock& s) { return (uint16_t)((s.hdr[18] << 8) | s.hdr[19]); }
+FS_HD inline fs_tx_sock_out out_of(const fs_tx_sock& s, const Plan& p, uint64_t first_frame) {
     fs_tx_sock_out o;
     o.snd_nxt = s.snd_nxt + p.data + (p.fin ? 1u : 0u);
     o.ring_rpos = (uint32_t)(((uint64_t)s.ring_rpos + p.data) % s.ring_size);
@@ -122,7 +124,7 @@ inline fs_tx_sock_out out_of(const fs_tx_sock& s, const Plan& p, uint64_t first_
     return o;
 }
 // bytes of `frames` a socket's S > 0 frames own: S - 1 full frames and the last one
-inline uint64_t sock_bytes(const fs_tx_sock& s, const Plan& p, uint32_t flags, uint32_t align) {
+FS_HD inline uint64_t sock_bytes(const fs_tx_sock& s, const Plan& p, uint32_t flags, uint32_t align) {
     return (uint64_t)(p.frames - 1) * segment::slot_bytes(segment::kTcpHdr + s.mss, flags, align) +
            segment::slot_bytes(segment::kTcpHdr + chunk_of(s, p, p.frames - 1), flags, align);
 }
@@ -205,11 +207,11 @@ static_assert(offsetof(RingRec, hdr) == offsetof(segment::SendRec, hdr) &&
                   offsetof(RingRec, id_at) == offsetof(segment::SendRec, id_at),
               "RingRec and SendRec agree in what the shared frame body reads");
 
-inline segment::Block block_of(uint32_t n_recs, uint64_t id_entries) {
+FS_HD inline segment::Block block_of(uint32_t n_recs, uint64_t id_entries) {
     return segment::block_of(n_recs, sizeof(RingRec), id_entries);
 }
 
-inline void put32(uint8_t* p, uint32_t v) {
+FS_HD inline void put32(uint8_t* p, uint32_t v) {
     p[0] = (uint8_t)(v >> 24);
     p[1] = (uint8_t)(v >> 16);
     p[2] = (uint8_t)(v >> 8);
@@ -217,7 +219,7 @@ inline void put32(uint8_t* p, uint32_t v) {
 }
 // The header of a socket's frames as the kernel takes it: the template with Seq, Ack, the flags of the
 // last frame and the window.
-inline void put_state(const fs_tx_sock& s, const Plan& p, uint8_t hdr[54]) {
+FS_HD inline void put_state(const fs_tx_sock& s, const Plan& p, uint8_t hdr[54]) {
     memcpy(hdr, s.hdr, 54);
     put32(hdr + 38, s.snd_nxt);
     put32(hdr + 42, s.rcv_nxt);

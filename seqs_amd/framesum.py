@@ -38,6 +38,9 @@ from .abi import (  # noqa: F401 (re-exported: this module is the binding's publ
     ARP_ANSWERED, ARP_FRAME, ARP_FRAME_PADDED, ARP_FULL, ARP_HOST_DTYPE, ARP_HOST_OUT_DTYPE, ARP_IGNORED, ARP_MAX_HOSTS,
     ARP_MAX_QUERIES, ARP_MAX_REPLY_SLOTS, ARP_NONE, ARP_NOT_ARP, ARP_PAD, ARP_PROTOTYPES, ARP_Q_DONE, ARP_Q_SENT, ARP_Q_WAIT,
     ARP_QUERY_DTYPE, ARP_QUERY_OUT_DTYPE, ARP_RESOLVED, ARP_SEND_REQUEST, ARP_STALE, ARP_UNSUPPORTED,
+    SEND_RESIDENT_PROTOTYPES, TX_TOTALS_DTYPE, TX_WRITEBACK, TX_DEFERRED, TX_INVALID, TX_NO_RX,
+    TX_BAD_ETHERTYPE, TX_BAD_IHL, TX_BAD_PROTO, TX_BAD_DATA_OFFSET, TX_BAD_MSS, TX_BAD_SOCK_FLAGS, TX_BAD_MAX_FRAMES,
+    TX_BAD_RING_SIZE, TX_BAD_RING_POS, TX_BAD_BUFFERED, TX_BAD_RING_RANGE, TX_BAD_RX_INDEX,
 )
 
 _vp, _u64 = ctypes.c_void_p, ctypes.c_uint64
@@ -998,6 +1001,73 @@ class Engine(_Handle):
         uint32, digests, status, socks_out) numpy arrays."""
         return self._send_rings(True, socks, rings, mtu, flags, align, frames, None)
 
+    # ---- the ring send from device-resident sockets (include/framesum_send_resident.h) ----
+    def send_rings_resident(self, socks, rings, frames_cap: int, frames=None, frames_bytes: Optional[int] = None,
+                            rx_socks_out=None, rx_snd_out=None, rx_index=None, writeback: bool = False, mtu: int = 0,
+                            flags: int = 0, align: int = 1, stream=None, offsets=None, lengths=None, out=None, status=None,
+                            socks_out=None, totals=None):
+        """The ring send with its socket table on the device (fs_send_rings_resident). `socks`: an (n, 104)
+        uint8 CUDA tensor of TX_SOCK_DTYPE records (tx_socks_tensor makes one), only read unless
+        `writeback` (TX_WRITEBACK), which writes every built socket's state after the call back into it.
+        `rx_socks_out`, `rx_snd_out`: the socks_out and snd_out tensors of an RX call (recv_flows_device, ...)
+        passed straight in: rcv_nxt, rcv_wnd, snd_una, snd_wnd and the owed ACK are taken from them on the
+        device, socket i from record rx_index[i] (an int32 / uint32 tensor; TX_NO_RX: none) or i. The
+        checks, the rule and the layout run in kernels: an invalid socket is reported in its record
+        (TX_INVALID | reason << 16), and sockets whose frames no longer fit `frames_cap` frames or
+        `frames_bytes` bytes (default: all of `frames`) are TX_DEFERRED: call again for them. `frames`: a
+        uint8 CUDA tensor to build into (required unless frames_bytes is given: then a new one of that
+        size). offsets, lengths, out, status: False leaves one out, None makes a new tensor of frames_cap
+        entries. Returns (frames, offsets int64, lengths int32, out (n, 2) int32, status uint8, socks_out
+        (n, 32) uint8, totals (40,) uint8) device tensors; split_tx brings the last two to the host.
+        Asynchronous on `stream`: nothing is read back."""
+        import torch
+
+        dev = rings.device
+        assert socks.is_cuda and socks.dtype == torch.uint8 and socks.is_contiguous() and socks.dim() == 2 and \
+            socks.shape[1] == TX_SOCK_DTYPE.itemsize, "socks is an (n, 104) uint8 CUDA tensor"
+        assert rings.is_cuda and rings.dtype == torch.uint8 and rings.is_contiguous()
+        n = int(socks.shape[0])
+        if frames is None:
+            assert frames_bytes is not None, "pass `frames`, or frames_bytes for a new buffer"
+            frames = torch.empty((int(frames_bytes),), dtype=torch.uint8, device=dev)
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous()
+        if frames_bytes is None:
+            frames_bytes = int(frames.numel())
+        assert frames_bytes <= int(frames.numel())
+        cap = int(frames_cap)
+        made = {"offsets": lambda: torch.empty((cap,), dtype=torch.int64, device=dev),
+                "lengths": lambda: torch.empty((cap,), dtype=torch.int32, device=dev),
+                "out": lambda: torch.empty((cap, 2), dtype=torch.int32, device=dev),
+                "status": lambda: torch.empty((cap,), dtype=torch.uint8, device=dev)}
+        arrays = []
+        for name, given in (("offsets", offsets), ("lengths", lengths), ("out", out), ("status", status)):
+            t = made[name]() if given is None else (None if given is False else given)
+            assert t is None or (t.is_cuda and t.is_contiguous() and t.shape[0] >= cap), name
+            arrays.append(t)
+        if socks_out is None:
+            socks_out = torch.empty((n, TX_SOCK_OUT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if totals is None:
+            totals = torch.empty((TX_TOTALS_DTYPE.itemsize,), dtype=torch.uint8, device=dev)
+        assert socks_out.is_cuda and socks_out.is_contiguous() and socks_out.numel() * socks_out.element_size() >= 32 * n
+        assert totals.is_cuda and totals.is_contiguous() and totals.numel() * totals.element_size() >= 40
+        n_rx = 0
+        for t in (rx_socks_out, rx_snd_out, rx_index):
+            assert t is None or (t.is_cuda and t.is_contiguous())
+        if rx_socks_out is not None:
+            n_rx = int(rx_socks_out.numel() * rx_socks_out.element_size()) // SOCK_OUT_DTYPE.itemsize
+            assert rx_snd_out is None or rx_snd_out.numel() * rx_snd_out.element_size() >= n_rx * SND_OUT_DTYPE.itemsize
+        if rx_index is not None:
+            assert rx_index.element_size() == 4 and rx_index.numel() >= n
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        opt = lambda t: None if t is None else _tensor_ptr(t)  # noqa: E731
+        st = self.lib.fs_send_rings_resident(
+            self._ctx, _tensor_ptr(socks), n, opt(rx_socks_out), opt(rx_snd_out), opt(rx_index), n_rx, _tensor_ptr(rings),
+            int(rings.numel()), mtu, flags | (TX_WRITEBACK if writeback else 0), align, _tensor_ptr(frames), frames_bytes, cap,
+            *map(opt, arrays), _tensor_ptr(socks_out), _tensor_ptr(totals), _stream_ptr(stream))
+        self._check(st, "fs_send_rings_resident")
+        return (frames, *arrays, socks_out, totals)
+
     # ---- host-staged path (numpy in, numpy out) -----------------------------
     def host_empty(self, shape, dtype=np.uint8) -> np.ndarray:
         """A numpy array in pinned host memory (fs_host_alloc), freed with the array."""
@@ -1154,6 +1224,23 @@ def tx_sock_from(sock_out, tx=None, snd_out=None, **fields) -> np.ndarray:
         res["snd_una"], res["snd_wnd"] = snd_out["snd_una"], snd_out["snd_wnd"]
         res["flags"] |= np.where(snd_out["flags"] & RECV_ACK_OWED, TX_ACK, 0).astype(np.uint32)
     return res
+
+
+def tx_socks_tensor(socks: np.ndarray, device):
+    """A TX_SOCK_DTYPE array as the (n, 104) uint8 tensor on `device` that send_rings_resident takes."""
+    import torch
+
+    socks = np.ascontiguousarray(socks, dtype=TX_SOCK_DTYPE).reshape(-1)
+    raw = socks.view(np.uint8).reshape(socks.size, TX_SOCK_DTYPE.itemsize)
+    return torch.from_numpy(raw.copy()).to(device)
+
+
+def split_tx(socks_out, totals, socks=None):
+    """The host view of send_rings_resident's `socks_out` and `totals` tensors (this waits for them):
+    (TX_SOCK_OUT_DTYPE[n_socks], the TX_TOTALS_DTYPE record), and with `socks` (the table's tensor) the
+    TX_SOCK_DTYPE array it holds as a third."""
+    res = (_records(socks_out, TX_SOCK_OUT_DTYPE), _records(totals, TX_TOTALS_DTYPE)[0])
+    return res if socks is None else (*res, _records(socks, TX_SOCK_DTYPE))
 
 
 def _records(t, dtype) -> np.ndarray:
